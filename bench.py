@@ -26,10 +26,18 @@ on a one-GPU box (with ``--backend gloo`` in process mode).  value = packets pro
 GPUs / wall time (max over ranks).  The line also reports the host time spent
 enqueueing a step, per GPU.
 
-Also reported: the dominant kernel's roofline (HIP events on the bundle
-stream, algorithmic bytes L + (L+T) per packet), and a CPU baseline: the
-oracle's pinned C timing loop (oracle/oracle_bench.c) in the reference's call
-structure and a tuned-OpenSSL variant, on one core and on the box's CPU share.
+A plain run does what `value` needs and no more: it stages the bundles, warms
+up (40 serial run-in steps for the GPU's clocks, then ``--warmup`` steps),
+times the steps and prints the JSON line.  ``--dump-outputs DIR`` also
+writes what the last timed step handed back (Side.dump) as DIR/<name>.npy; the
+inputs are seeded, so two builds can be compared output for output.
+
+``--full`` adds everything else: the dominant kernel's roofline (HIP events on
+the bundle stream during the run-in steps, algorithmic bytes L + (L+T) per
+packet, a device-copy bandwidth probe), a CPU baseline (the oracle's pinned C
+timing loop, oracle/oracle_bench.c, in the reference's call structure and a
+tuned-OpenSSL variant, on one core and on the host's CPU share), the
+pinned-host end-to-end leg and the dispatcher leg.
 """
 from __future__ import annotations
 
@@ -45,6 +53,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 RING = 160  # most distinct bundles staged in HBM per GPU (x 319 MB at the default size)
 sys.path.insert(0, ROOT)
+DUMP_PACKETS = 4096  # --dump-outputs: most packets whose regions are written
+DUMP_SEED = 0x5EED0D00  # ... and the seed of their choice
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 METRIC = "SRTP protect+unprotect packets/s + GB/s, 1200B AES_CM_128_HMAC_SHA1_80, 1-8 GPU"
@@ -55,6 +65,13 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: stage timing and roofline, the "
+                         "CPU baseline, the end-to-end and dispatcher legs (each can be switched "
+                         "off with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy "
+                         "(float32 / float64; a fixed, seeded sample of the packets)")
     ap.add_argument("--packets", type=int, default=1 << 18, help="bundle size per GPU")
     ap.add_argument("--ssrcs", type=int, default=10000, help="concurrent SSRCs per GPU")
     ap.add_argument("--keysets", type=int, default=1,
@@ -69,11 +86,13 @@ def parse_args():
                     help="CPU baseline: seconds per measurement (4 measurements)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = the box's CPU share: min(16, CPUs in the affinity set)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the pinned-host end-to-end leg")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true",
+                    help="with --full: skip the pinned-host end-to-end leg")
     ap.add_argument("--e2e-bundles", type=int, default=24)
     ap.add_argument("--no-dispatch", action="store_true",
-                    help="skip the dispatcher leg (host bundles through srtp_dispatch_transform_host)")
+                    help="with --full: skip the dispatcher leg (host bundles through "
+                         "srtp_dispatch_transform_host)")
     ap.add_argument("--dispatch-shards", default="",
                     help="comma-separated shard counts of the dispatcher leg (default: 1,2,4 on one "
                          "GPU, else the GPU count)")
@@ -515,6 +534,7 @@ class Side:
             self.reuse = total + 1 > self.ring
             self.ev_free = [mkev() for _ in range(self.ring)] if self.reuse else []
             self.pending = None  # join mode: protected bundle whose unprotect is due
+            self.last_p = self.last_u = None  # the last bundle protected / unprotected (dump)
             base = torch.from_numpy(b.seg).to(dev)
             len0 = torch.from_numpy(b.length.view(np.int32)).to(dev)
             self.segs, self.lens = [], []
@@ -546,9 +566,11 @@ class Side:
                 self.advance_seq(self.segs[j], self.ring)
         self.eng.transform_device(False, self.tid_s, self.segs[j], self.off, self.lens[j],
                                   self.cap, self.st, stream=stream)
+        self.last_p = i
 
     def unprotect(self, i, stream):
         j = i % self.ring
+        self.last_u = i
         self.eng_r.transform_device(True, self.tid_r, self.segs[j], self.off, self.lens[j],
                                     self.cap, self.st_r, stream=stream)
         if self.reuse:
@@ -605,6 +627,58 @@ class Side:
 
     def bad(self):
         return int((self.st != 0).sum()) + int((self.st_r != 0).sum())
+
+    def dump(self, out_dir, tag=""):
+        """--dump-outputs: what the last timed step handed back, as
+        out_dir/<name><tag>.npy (float32; sample_index float64).  Called after
+        the timed steps, before finish().
+
+        protect_status / unprotect_status: the step's two status arrays.
+        unprotect_len / unprotect_packets: the bundle its unprotect ran on, the
+        packets' lengths and their regions of the segment (cap bytes each).
+        Everything is in place, so with protect(i) and unprotect(i) in one step
+        (every mode but --pipe join) this is bundle i after its round trip: the
+        restored packet, and past the restored length the tag protect wrote
+        (HMAC over the ciphertext and the ROC).  In join mode the step
+        unprotects bundle i - 1, and bundle i is still protected: it is
+        written as protect_len / protect_packets.
+
+        Regions are those of a fixed seeded choice of packets (sample_index:
+        DUMP_PACKETS at most, and at most 16 MiB per array); statuses and
+        lengths are every packet's up to 2^20 packets, else the sample's.
+        Under 64 MB in all."""
+        torch = self.torch
+        os.makedirs(out_dir, exist_ok=True)
+        cap = int(self.b.cap.max())
+        k = max(1, min(self.n, DUMP_PACKETS, (16 << 20) // (4 * cap)))
+        sel = np.sort(np.random.default_rng(DUMP_SEED).choice(self.n, k, replace=False))
+
+        def save(name, a):
+            np.save(os.path.join(out_dir, f"{name}{tag}.npy"), a)
+
+        with torch.cuda.device(self.dev):
+            torch.cuda.synchronize(self.dev)
+            sel_t = torch.from_numpy(sel).to(self.dev)
+            pick = slice(None) if self.n <= 1 << 20 else sel_t
+            # a region's bytes past its own cap (variable lengths) are left out as 0
+            col = torch.arange(cap, device=self.dev)[None, :]
+            inside = col < self.cap[sel_t].to(torch.int64)[:, None]
+            idx = (self.off64[sel_t][:, None] + col) * inside
+
+            def f32(t):
+                return t.to(torch.float32).cpu().numpy()
+
+            save("sample_index", sel.astype(np.float64))
+            save("protect_status", f32(self.st[pick]))
+            save("unprotect_status", f32(self.st_r[pick]))
+            if self.last_u is not None:
+                j = self.last_u % self.ring
+                save("unprotect_len", f32(self.lens[j][pick]))
+                save("unprotect_packets", f32(self.segs[j][idx] * inside))
+            if self.last_p is not None and self.last_p != self.last_u:
+                j = self.last_p % self.ring
+                save("protect_len", f32(self.lens[j][pick]))
+                save("protect_packets", f32(self.segs[j][idx] * inside))
 
     def engines(self):
         return [self.eng] if self.eng_r is self.eng else [self.eng, self.eng_r]
@@ -686,7 +760,7 @@ def main():
     if args.dispatch_child:
         sys.exit(dispatch_child(args))
     child = None
-    if world == 1 and not args.no_dispatch and not args.dispatch_in_process:
+    if args.full and world == 1 and not args.no_dispatch and not args.dispatch_in_process:
         # the dispatcher leg's torch-free process, started before this one
         # touches a GPU (dispatch_child)
         child = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--dispatch-child"] + sys.argv[1:],
@@ -698,6 +772,26 @@ def main():
         if child is not None and child.poll() is None:
             child.kill()
             child.communicate()
+
+
+def copy_bandwidth(torch, dev):
+    """Achievable HBM bandwidth on this device (plain device-to-device copy of
+    512 MiB, read + write bytes), reported beside the 8 TB/s spec peak."""
+    try:
+        with torch.cuda.device(dev):
+            src = torch.empty(1 << 29, dtype=torch.uint8, device=dev)
+            dst = torch.empty_like(src)
+            dst.copy_(src)
+            torch.cuda.synchronize(dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(5):
+                dst.copy_(src)
+            e1.record()
+            torch.cuda.synchronize(dev)
+            return round(5 * 2 * src.numel() / (e0.elapsed_time(e1) / 1e3) / 1e9, 1)
+    except Exception:
+        return None
 
 
 def run_bench(args, world, child):
@@ -730,7 +824,8 @@ def run_bench(args, world, child):
     pols = policies(args)
     n, L = args.packets, args.len
     T = pols[0].authTagLength
-    n_timing = 40  # serial stage-timing steps (also the GPU's run-in before the warmup)
+    # serial run-in steps before the warmup (--full: also the stage-timing steps)
+    n_timing = 40
     total = n_timing + args.warmup + args.steps
     sides = [Side(torch, d, rank if mode == "process" else i, args, pols, total)
              for i, d in enumerate(devices)]
@@ -739,32 +834,16 @@ def run_bench(args, world, child):
     for sd in sides:  # loads the status-check kernels now, not between passes
         sd.bad()
 
-    # achievable HBM bandwidth on this device (plain device-to-device copy of
-    # 512 MiB, read + write bytes), reported beside the 8 TB/s spec peak
-    copy_gbs = None
-    try:
-        with torch.cuda.device(sd0.dev):
-            src = torch.empty(1 << 29, dtype=torch.uint8, device=sd0.dev)
-            dst = torch.empty_like(src)
-            dst.copy_(src)
-            torch.cuda.synchronize(sd0.dev)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(5):
-                dst.copy_(src)
-            e1.record()
-            torch.cuda.synchronize(sd0.dev)
-            copy_gbs = round(5 * 2 * src.numel() / (e0.elapsed_time(e1) / 1e3) / 1e9, 1)
-            del src, dst
-    except Exception:
-        copy_gbs = None
+    copy_gbs = copy_bandwidth(torch, sd0.dev) if args.full else None
 
-    # 1. Per-stage HIP-event timing (the roofline kernels' launch durations),
-    # untimed, serial on the first GPU (one stream: no stage shares the GPU
-    # with the other direction).  It runs right before the warmup, so that the
-    # GPU is busy, every kernel is loaded and the clocks are up when it starts.
+    # 1. The run-in: untimed serial steps right before the warmup, so that the
+    # GPU is busy, every kernel is loaded and the clocks are up when it starts
+    # (a 20-step run without them read 7 % below the same run with them).  --full
+    # takes the per-stage HIP-event timing (the roofline kernels' launch
+    # durations) in them, on the first GPU: one stream, so no stage shares the
+    # GPU with the other direction.
     engines = [sd0.eng] if sd0.eng_r is sd0.eng else [sd0.eng, sd0.eng_r]
-    for e in engines:
+    for e in engines if args.full else []:
         e.set_timing(True)
         e.read_timing()
     for _ in range(n_timing):
@@ -775,7 +854,7 @@ def run_bench(args, world, child):
             sd.serial_step(k)
     torch.cuda.synchronize(sd0.dev)
     timing = {}
-    for e in engines:
+    for e in engines if args.full else []:
         for key, (ms, cnt) in e.read_timing().items():
             m0, c0 = timing.get(key, (0.0, 0))
             timing[key] = (m0 + ms, c0 + cnt)
@@ -798,6 +877,10 @@ def run_bench(args, world, child):
         dist.barrier()
     g += args.warmup + args.steps
     dt = t_end - t_start
+    if args.dump_outputs:
+        for i, sd in enumerate(sides):
+            shard = rank if mode == "process" else i
+            sd.dump(args.dump_outputs, f"_gpu{shard}" if n_gpus > 1 else "")
     for sd in sides:
         sd.finish()
     sub1, ok1 = status_counts(sides)
@@ -813,7 +896,7 @@ def run_bench(args, world, child):
     dt_max = float(t.item())
     # slow-path work per bundle over the whole run (run-in, warmup, timed steps)
     slow = {"long_walked": 0, "repaired": 0, "roc_rechecks": 0, "bundles": 0}
-    for e in engines:  # the first GPU's engines
+    for e in engines if args.full else []:  # the first GPU's engines
         s = e.stats()
         for k in slow:
             slow[k] += s[k]
@@ -828,7 +911,7 @@ def run_bench(args, world, child):
 
     pmc = {}
     pmc_path = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(pmc_path):
+    if args.full and os.path.exists(pmc_path):
         try:
             with open(pmc_path) as f:
                 pmc = json.load(f)
@@ -839,7 +922,7 @@ def run_bench(args, world, child):
     # the counters are of the build whose kernel sources hash to this; another
     # build's counters are reported as stale (traffic_stale), not as this one's
     from libjitsi_amd._native import kernel_source_sha16
-    ksha = kernel_source_sha16()
+    ksha = kernel_source_sha16() if args.full else None
     pmc_stale = bool(pmc) and pmc.get("kernel_source_sha16") != ksha
 
     def roofline(stage, kernel, traffic_key, util_key=None):
@@ -888,17 +971,17 @@ def run_bench(args, world, child):
     other = [r for r in cands if r is not dominant]
 
     cpu = None
-    if rank == 0 and n_gpus == 1 and not args.no_cpu:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu:
         share = args.cpu_threads or max(1, min(16, len(os.sched_getaffinity(0))))
         cpu = cpu_baseline(args.cpu_seconds, share, L, args.ssrcs, T)
 
-    # 3. The PCIe-inclusive legs (never `value`): every GPU's pinned pipeline at
-    # once, and the dispatcher's host-bundle path.
+    # 3. (--full) The PCIe-inclusive legs (never `value`): every GPU's pinned
+    # pipeline at once, and the dispatcher's host-bundle path.
     b0, keys0 = sd0.b, sd0.keys
     del sides, sd0
     torch.cuda.empty_cache()
     e2e = None
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         legs = [E2E(b0, pols, keys0, n, d) for d in devices]
         for x in legs:
             x.warm()
@@ -937,7 +1020,7 @@ def run_bench(args, world, child):
             x.close()
         e2e = e2e_summary(e_dt, e_pk, e_by, e_ok, n_gpus, args.e2e_bundles, legs[0].depth)
     disp = disp_torch = None
-    if rank == 0 and not args.no_dispatch and world == 1:
+    if args.full and rank == 0 and not args.no_dispatch and world == 1:
         counts, devs_for = dispatch_plan(args, devices)
         if child is None:
             disp = dispatch_leg(b0, pols, keys0, n, devs_for, counts, args.dispatch_bundles)
@@ -959,6 +1042,7 @@ def run_bench(args, world, child):
             "n_gpus": n_gpus,
             "steps": args.steps,
             "warmup": args.warmup,
+            "run_in_steps": n_timing,
             "ms_per_step": round(dt_max / args.steps * 1e3, 4),
             "higher_is_better": True,
             "scaling": "weak",
@@ -982,16 +1066,22 @@ def run_bench(args, world, child):
             "gbps": round(gbs, 2),
             "goodput_gbps": round(pps * L * 2 / 1e9, 2),
             "all_accepted": ok,
-            "stage_ms": {k: round(v, 4) for k, v in stages.items()},
-            "slow_path_per_bundle": slow_per_bundle,
             "host_enqueue_us_per_step": enqueue_us,
-            "roofline": dominant,
-            "roofline_other": other[0] if other else None,
-            "cpu_baseline": cpu,
-            "e2e": e2e,
-            "dispatch": disp,
-            "dispatch_in_torch_process": disp_torch,
+            "full": args.full,
         }
+        if args.full:
+            line.update({
+                "stage_ms": {k: round(v, 4) for k, v in stages.items()},
+                "slow_path_per_bundle": slow_per_bundle,
+                "roofline": dominant,
+                "roofline_other": other[0] if other else None,
+                "cpu_baseline": cpu,
+                "e2e": e2e,
+                "dispatch": disp,
+                "dispatch_in_torch_process": disp_torch,
+            })
+        if args.dump_outputs:
+            line["outputs"] = args.dump_outputs
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -1,5 +1,5 @@
 """bench.py's host-side plumbing on CPU: the torch-free dispatcher child
-(bench.py dispatch_child: started before the bench touches a GPU, idle until
+(bench.py --full, dispatch_child: started before the bench touches a GPU, idle until
 "go", never imports torch) and the parent's collection of its JSON line."""
 import json
 import os
@@ -15,7 +15,7 @@ import bench  # noqa: E402
 def test_dispatch_child_idle_exit_without_torch():
     # EOF on stdin (the parent died or ran --no-dispatch): the child exits 0
     # without a GPU call and without ever importing torch
-    code = ("import io, sys; sys.argv = ['bench.py', '--dispatch-child', '--packets', '4096']; "
+    code = ("import io, sys; sys.argv = ['bench.py', '--dispatch-child', '--full', '--packets', '4096']; "
             "sys.stdin = io.StringIO(''); import bench; rc = bench.dispatch_child(bench.parse_args()); "
             "print(json.dumps({'rc': rc, 'torch': 'torch' in sys.modules}))")
     out = subprocess.run([sys.executable, "-c", "import json; " + code], cwd=ROOT, capture_output=True,

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 O=gpurun_out/${TAG:-run}
 mkdir -p "$O"
 PYT="python -u -m pytest -x -q --timeout 120 --timeout-method thread -p no:cacheprovider"
-BENCH="python bench.py --no-cpu --no-e2e --no-dispatch"
+BENCH="python bench.py --full --no-cpu --no-e2e --no-dispatch"  # --full: the recipes read stage_ms
 
 step() {  # step <name> <seconds> <cmd...>: output in $O/<name>.log
     local name=$1 t=$2
@@ -38,7 +38,7 @@ recipe() {
     dispatch_tests) step dispatch_tests 600 $PYT -m gpu tests/test_host_memory.py tests/test_dispatcher.py \
                       tests/test_dispatch_async.py tests/test_config5_sharded.py tests/test_rawpacket.py ;;
     # the dispatcher leg alone (host bundles, 1/2/4 shards on one GPU), in its torch-free child
-    bench_dispatch) step bench_dispatch 600 python bench.py --steps 5 --warmup 2 --no-cpu --no-e2e &&
+    bench_dispatch) step bench_dispatch 600 python bench.py --full --steps 5 --warmup 2 --no-cpu --no-e2e &&
                     tail -1 "$O/bench_dispatch.log" | python3 -c 'import json,sys; d=json.loads(sys.stdin.read())
 for k, v in (d["dispatch"] or {}).items():
     if isinstance(v, dict): print(k, v.get("directional_pps"), v.get("host_ms_per_bundle"))' | tee "$O/dispatch.txt" ;;
@@ -111,7 +111,7 @@ for l in open('$O/agg_ab.jsonl'):
     bench)        step bench 300 $BENCH --steps 20 --warmup 5 && tail -1 "$O/bench.log" > "$O/bench.json" ;;
     bench_fused)  SRTP_TEST_DEBUG=4 step bench_fused 300 $BENCH --steps 20 --warmup 5 ;;
     bench_serial) step bench_serial 300 $BENCH --steps 20 --warmup 5 --serial ;;
-    bench_default) step bench_default 600 python bench.py && tail -1 "$O/bench_default.log" > "$O/bench_default.json" ;;
+    bench_default) step bench_default 600 python bench.py --full && tail -1 "$O/bench_default.log" > "$O/bench_default.json" ;;
     trace)        step trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -o run -- \
                       python3 bench.py --steps 20 --warmup 2 --no-cpu --no-e2e --no-dispatch --serial ;;
     trace_default) step trace_default 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace_default" \
