@@ -72,6 +72,17 @@ extern "C" {
 #define SRTP_AESF8_ENCRYPTION 2 /* SRTPCipherF8 (SDES F8_128_HMAC_SHA1_80) */
 #define SRTP_TWOFISH_ENCRYPTION 3   /* counter mode over Twofish (ZRTP "2FS") */
 #define SRTP_TWOFISHF8_ENCRYPTION 4 /* F8 over Twofish */
+/* AES-GCM, the AEAD profiles of RFC 7714 (AEAD_AES_128_GCM / AEAD_AES_256_GCM;
+ * later libjitsi's SRTPPolicy.AESGCM_ENCRYPTION).  The policy shape is
+ * {SRTP_AESGCM_ENCRYPTION, enc_key_len 16 or 32, SRTP_NULL_AUTHENTICATION,
+ * auth_key_len 0, auth_tag_len 16, salt_key_len 12}.
+ * What exists for it is the host side: the key derivation of RFC 7714 11
+ * (srtp_derive_session_keys_for), the AEAD itself (srtp_aes_gcm) and the
+ * dispatcher's may-throw test (srtp_packet_may_throw, tag_mask bit 16).  The
+ * engine has no kernel for it yet: srtp_factory_create still answers
+ * SRTP_EPOLICY for such a policy, and srtp_dtls_profile_keys for the two
+ * DTLS-SRTP ids (SRTP_PROFILE_AEAD_AES_*_GCM below). */
+#define SRTP_AESGCM_ENCRYPTION 5
 #define SRTP_NULL_AUTHENTICATION 0
 #define SRTP_HMACSHA1_AUTHENTICATION 1
 #define SRTP_SKEIN_AUTHENTICATION 2 /* Skein-512 MAC, tag_len * 8 output bits (ZRTP "SK32"/"SK64") */
@@ -754,6 +765,15 @@ int srtp_skein512_mac(const uint8_t *key, int32_t key_len, int32_t out_bits, con
 int srtp_block_encrypt(int32_t enc_type, const uint8_t *key, int32_t key_len, const uint8_t in[16],
                        uint8_t out[16]);
 
+/* AES-GCM one-shot on the host (NIST SP 800-38D with a 96-bit IV and a
+ * 16-byte tag, the form RFC 7714 5 uses): seals data[0, len) in place under
+ * key (16 or 32 bytes) with the additional data aad and writes tag; with
+ * `open` set it opens instead -- returns 1 on a tag mismatch, leaving data
+ * untouched, else deciphers.  GHASH runs by Shoup's 4-bit method: the
+ * 16-entry table a GPU pass would take per key set (host_crypto.h). */
+int srtp_aes_gcm(int32_t open, const uint8_t *key, int32_t key_len, const uint8_t iv[12],
+                 const uint8_t *aad, int32_t aad_len, uint8_t *data, int32_t len, uint8_t tag[16]);
+
 /* DTLS-SRTP keying (control plane, host only): what
  * DtlsPacketTransformer.initializeSRTPTransformer does after the handshake
  * (transform/dtls/DtlsPacketTransformer.java:549-690).
@@ -786,6 +806,10 @@ int srtp_block_encrypt(int32_t enc_type, const uint8_t *key, int32_t key_len, co
 #define SRTP_PROFILE_AES128_CM_HMAC_SHA1_32 0x0002
 #define SRTP_PROFILE_NULL_HMAC_SHA1_80 0x0005
 #define SRTP_PROFILE_NULL_HMAC_SHA1_32 0x0006
+/* RFC 7714 14.2 (16- / 32-byte key, 12-byte salt, 16-byte tag): the ids only;
+ * srtp_dtls_profile_keys does not know them until the engine runs AES-GCM */
+#define SRTP_PROFILE_AEAD_AES_128_GCM 0x0007
+#define SRTP_PROFILE_AEAD_AES_256_GCM 0x0008
 #define SRTP_TLS_PRF_TLS10 0
 #define SRTP_TLS_PRF_SHA256 1
 #define SRTP_DTLS_EXPORTER_LABEL "EXTRACTOR-dtls_srtp"

@@ -16,6 +16,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "srtp_mi355x.h")
 
 # include/srtp_mi355x.h
 NULL_ENCRYPTION, AESCM_ENCRYPTION, AESF8_ENCRYPTION, TWOFISH_ENCRYPTION, TWOFISHF8_ENCRYPTION = range(5)
+AESGCM_ENCRYPTION = 5  # RFC 7714 AEAD_AES_128_GCM / AEAD_AES_256_GCM
+PROFILE_AEAD_AES_128_GCM, PROFILE_AEAD_AES_256_GCM = 0x0007, 0x0008
 NULL_AUTHENTICATION, HMACSHA1_AUTHENTICATION = 0, 1
 KIND_RTP, KIND_RTCP = 0, 1
 (STATUS_OK, STATUS_DROP_REPLAY, STATUS_DROP_AUTH, STATUS_DROP_VERSION, STATUS_DROP_NO_CONTEXT,
@@ -55,7 +57,7 @@ EXPORTED = [
     "srtp_dispatch_get_context_state", "srtp_dispatch_set_context_state", "srtp_dispatch_stats",
     "srtp_tls_export_keying_material", "srtp_dtls_profile_keys", "srtp_dtls_transformer_create",
     "srtp_engine_get_opts", "srtp_derive_session_keys_n", "srtp_derive_session_keys_for",
-    "srtp_block_encrypt", "srtp_aggregator_opts_default", "srtp_aggregator_create",
+    "srtp_block_encrypt", "srtp_aes_gcm", "srtp_aggregator_opts_default", "srtp_aggregator_create",
     "srtp_aggregator_submit", "srtp_aggregator_flush", "srtp_aggregator_stats",
     "srtp_aggregator_destroy", "srtp_derive_session_keys_auth", "srtp_skein512_mac",
     "srtp_engine_set_debug", "srtp_contexts_save", "srtp_contexts_restore",
@@ -194,6 +196,7 @@ def lib() -> C.CDLL:
     L.srtp_derive_session_keys_n.argtypes = [C.c_char_p, i32, C.c_char_p, i32, pu8, pu8, pu8]
     L.srtp_derive_session_keys_for.argtypes = [i32, C.c_char_p, i32, C.c_char_p, i32, pu8, pu8, pu8]
     L.srtp_block_encrypt.argtypes = [i32, C.c_char_p, i32, C.c_char_p, pu8]
+    L.srtp_aes_gcm.argtypes = [i32, C.c_char_p, i32, C.c_char_p, C.c_char_p, i32, pu8, i32, pu8]
     L.srtp_derive_session_keys_auth.argtypes = [i32, C.c_char_p, i32, C.c_char_p, i32, pu8, pu8, i32, pu8]
     L.srtp_skein512_mac.argtypes = [C.c_char_p, i32, i32, C.c_char_p, C.c_size_t, pu8]
     L.srtp_export_contexts.argtypes = [vp, i32, pu32, C.POINTER(CtxState), u32, pu32]

@@ -110,6 +110,10 @@ bool may_throw_one(bool rtp, int32_t reverse, const uint8_t *pkt, uint32_t L, ui
                    uint32_t tag_mask, int t_max) {
     if (rtp) {
         const int32_t h = rtp_header_len(pkt, C);
+        // Tag length 16 is AES-GCM's alone (the MACs stop at 12): its header is
+        // the AAD, so a header length that throws or is negative, or on
+        // protect one longer than the packet, is malformed whatever the flags
+        if ((tag_mask & (1u << 16)) && (h < 0 || (!reverse && (int32_t)L < h))) return true;
         if (!reverse) return cipher_may_throw(h, (int32_t)L - (h == kHdrThrow ? 0 : h));
         if (!(fl & (SRTP_PKT_FLAG_DISCARD | SRTP_PKT_FLAG_SILENCE)) || h == kHdrThrow) {
             for (int T = 0; T < 32; T++) {
@@ -722,7 +726,10 @@ int srtp_dispatch_factory_create(srtp_dispatch *d, int32_t sender, const uint8_t
     }, out);
     if (rc != SRTP_OK) return rc;
     for (const srtp_policy *p : {srtp, srtcp}) {
-        const int T = p->auth_type == SRTP_NULL_AUTHENTICATION ? 0 : p->auth_tag_len;
+        // AES-GCM (RFC 7714): NULL authentication, but its 16-byte AEAD tag
+        // shortens what unprotect looks at like a MAC's
+        const int T = p->auth_type == SRTP_NULL_AUTHENTICATION && p->enc_type != SRTP_AESGCM_ENCRYPTION
+                          ? 0 : p->auth_tag_len;
         if (T >= 0 && T < 32) d->tag_mask |= 1u << T;
     }
     return SRTP_OK;

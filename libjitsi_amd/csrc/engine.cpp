@@ -1256,8 +1256,25 @@ int srtp_derive_session_keys_for(int32_t enc_type, const uint8_t *mk, int32_t ke
                                  const uint8_t ms[14], int32_t rtcp, uint8_t *enc, uint8_t auth[20],
                                  uint8_t salt[14]) {
     if (!mk || !ms || !enc || !auth || !salt || (key_len != 16 && key_len != 32)) return SRTP_EINVAL;
+    if (enc_type == SRTP_AESGCM_ENCRYPTION) { // RFC 7714 11: 12-byte salts, no auth key
+        derive_session_keys_gcm(mk, key_len, ms, rtcp != 0, enc, salt);
+        memset(auth, 0, 20);
+        return SRTP_OK;
+    }
     derive_session_keys_cipher(is_twofish(enc_type), mk, key_len, ms, rtcp != 0, enc, auth, salt);
     return SRTP_OK;
+}
+
+int srtp_aes_gcm(int32_t open, const uint8_t *key, int32_t key_len, const uint8_t iv[12],
+                 const uint8_t *aad, int32_t aad_len, uint8_t *data, int32_t len, uint8_t tag[16]) {
+    if (!key || !iv || !tag || (key_len != 16 && key_len != 32) || aad_len < 0 || len < 0 ||
+        (!aad && aad_len) || (!data && len))
+        return SRTP_EINVAL;
+    uint32_t rk[60];
+    const int nr = aes_expand_le(key, key_len, rk);
+    const bool ok = aes_gcm(open != 0, rk, nr, iv, aad, (size_t)aad_len, data, (size_t)len, tag);
+    memset(rk, 0, sizeof rk);
+    return ok ? SRTP_OK : 1;
 }
 
 int srtp_derive_session_keys_auth(int32_t enc_type, const uint8_t *mk, int32_t key_len,

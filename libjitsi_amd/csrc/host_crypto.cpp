@@ -337,6 +337,124 @@ void derive_session_keys_cipher(bool twofish, const uint8_t *mk, int key_len, co
     memset(tT, 0, sizeof tT);
 }
 
+void derive_session_keys_gcm(const uint8_t *mk, int key_len, const uint8_t ms[12], bool rtcp,
+                             uint8_t *enc, uint8_t salt[14]) {
+    // RFC 7714 11: the 96-bit master salt padded on the right with 16 zero
+    // bits, then the RFC 3711 4.3 / RFC 6188 derivation; labels 0 / 3 (key)
+    // and 2 / 5 (salt, its first 96 bits); no auth key
+    uint8_t ms14[14] = {0}, auth[20], s14[14];
+    memcpy(ms14, ms, 12);
+    derive_session_keys_cipher(false, mk, key_len, ms14, rtcp, enc, auth, s14);
+    memcpy(salt, s14, 12);
+    salt[12] = salt[13] = 0;
+    memset(auth, 0, sizeof auth);
+    memset(s14, 0, sizeof s14);
+}
+
+// ------------------------------------------------------------------ AES-GCM
+namespace {
+inline uint64_t be64(const uint8_t *p) {
+    uint64_t v = 0;
+    for (int i = 0; i < 8; i++) v = (v << 8) | p[i];
+    return v;
+}
+inline void put_be64(uint8_t *p, uint64_t v) {
+    for (int i = 7; i >= 0; i--) { p[i] = (uint8_t)v; v >>= 8; }
+}
+// The reduction of the 4 bits shifted out of the low end: r times x^128 mod
+// the GCM polynomial, as the top 16 bits of the high half (0xe1 = 1 + x + x^2
+// + x^7 in GCM's reflected bit order).
+inline uint64_t gcm_reduce4(uint64_t r) { return ((r << 5) ^ (r << 10) ^ (r << 11) ^ (r << 12)) << 48; }
+} // namespace
+
+void gcm_htable(const uint8_t h[16], uint64_t tab[16][2]) {
+    uint64_t vh = be64(h), vl = be64(h + 8);
+    tab[0][0] = tab[0][1] = 0;
+    tab[8][0] = vl;
+    tab[8][1] = vh;
+    for (int i = 4; i > 0; i >>= 1) { // H x, H x^2, H x^3
+        const uint64_t t = (vl & 1) ? 0xe100000000000000ull : 0;
+        vl = (vh << 63) | (vl >> 1);
+        vh = (vh >> 1) ^ t;
+        tab[i][0] = vl;
+        tab[i][1] = vh;
+    }
+    for (int i = 2; i <= 8; i *= 2)
+        for (int j = 1; j < i; j++) {
+            tab[i + j][0] = tab[i][0] ^ tab[j][0];
+            tab[i + j][1] = tab[i][1] ^ tab[j][1];
+        }
+}
+
+void gcm_mult_xor(const uint64_t tab[16][2], uint8_t y[16], const uint8_t x[16]) {
+    uint8_t v[16];
+    for (int i = 0; i < 16; i++) v[i] = (uint8_t)(y[i] ^ x[i]);
+    const uint64_t xh = be64(v), xl = be64(v + 8);
+    uint64_t zh = 0, zl = 0;
+    for (int k = 0; k < 32; k++) { // nibbles from the last byte's low one up
+        const unsigned nib = (unsigned)((k < 16 ? xl >> (4 * k) : xh >> (4 * (k - 16))) & 15);
+        if (k) {
+            const uint64_t rem = zl & 15;
+            zl = (zh << 60) | (zl >> 4);
+            zh = (zh >> 4) ^ gcm_reduce4(rem);
+        }
+        zh ^= tab[nib][1];
+        zl ^= tab[nib][0];
+    }
+    put_be64(y, zh);
+    put_be64(y + 8, zl);
+}
+
+bool aes_gcm(bool open, const uint32_t *rk, int nr, const uint8_t iv[12], const uint8_t *aad,
+             size_t aad_len, uint8_t *data, size_t len, uint8_t tag[16]) {
+    uint8_t h[16] = {0}, y[16] = {0}, blk[16], ctr[16], ek0[16];
+    uint64_t tab[16][2];
+    aes_encrypt_block_nr(rk, nr, h, h);
+    gcm_htable(h, tab);
+    auto absorb = [&](const uint8_t *p, size_t n) {
+        for (size_t o = 0; o < n; o += 16) {
+            const size_t m = n - o < 16 ? n - o : 16;
+            memset(blk, 0, 16);
+            memcpy(blk, p + o, m);
+            gcm_mult_xor(tab, y, blk);
+        }
+    };
+    auto crypt = [&]() {
+        for (size_t o = 0; o < len; o += 16) {
+            const uint32_t c = (uint32_t)(o / 16) + 2u;
+            ctr[12] = (uint8_t)(c >> 24); ctr[13] = (uint8_t)(c >> 16);
+            ctr[14] = (uint8_t)(c >> 8); ctr[15] = (uint8_t)c;
+            aes_encrypt_block_nr(rk, nr, ctr, blk);
+            for (size_t i = 0; i < 16 && o + i < len; i++) data[o + i] ^= blk[i];
+        }
+    };
+    memcpy(ctr, iv, 12);
+    ctr[12] = ctr[13] = ctr[14] = 0;
+    ctr[15] = 1;
+    aes_encrypt_block_nr(rk, nr, ctr, ek0);
+    if (!open) crypt();
+    absorb(aad, aad_len);
+    absorb(data, len);
+    put_be64(blk, (uint64_t)aad_len * 8);
+    put_be64(blk + 8, (uint64_t)len * 8);
+    gcm_mult_xor(tab, y, blk);
+    for (int i = 0; i < 16; i++) y[i] ^= ek0[i];
+    bool ok = true;
+    if (open) {
+        uint8_t d = 0;
+        for (int i = 0; i < 16; i++) d |= (uint8_t)(y[i] ^ tag[i]);
+        ok = d == 0;
+        if (ok) crypt();
+    } else {
+        memcpy(tag, y, 16);
+    }
+    memset(h, 0, sizeof h);
+    memset(tab, 0, sizeof tab);
+    memset(ek0, 0, sizeof ek0);
+    memset(blk, 0, sizeof blk);
+    return ok;
+}
+
 void hmac_sha1_midstates(const uint8_t key[20], uint32_t ipad[5], uint32_t opad[5]) {
     uint8_t bi[64], bo[64];
     memset(bi, 0x36, 64);

@@ -58,4 +58,23 @@ void skein512_key_state(const uint8_t *key, int key_len, int out_bits, uint64_t 
 void skein512_mac(const uint8_t *key, int key_len, int out_bits, const uint8_t *msg, size_t n,
                   uint8_t *out);
 
+
+// AES-GCM (NIST SP 800-38D) with a 96-bit IV, as RFC 7714 uses it.  GHASH is
+// Shoup's 4-bit table method: tab[i] = {low, high} 64-bit halves (big-endian
+// bit order of the field element) of the 4-bit polynomial i times H, the table
+// the gfx950 kernel multiplies with (GcmKeys::htab).
+void gcm_htable(const uint8_t h[16], uint64_t tab[16][2]);
+// y = (y ^ x) * H with that table (y, x: 16 bytes).
+void gcm_mult_xor(const uint64_t tab[16][2], uint8_t y[16], const uint8_t x[16]);
+// Seal (open = false) or open data[0, len) in place under the expanded key
+// rk / nr; tag[16] is written (seal) or compared (open: returns false on a
+// mismatch and leaves data untouched).
+bool aes_gcm(bool open, const uint32_t *rk_le, int nr, const uint8_t iv[12], const uint8_t *aad,
+             size_t aad_len, uint8_t *data, size_t len, uint8_t tag[16]);
+// RFC 7714 11: the session encryption key (key_len bytes) and the 12-byte
+// session salt (salt[12..13] = 0) from a 12-byte master salt, by the AES-CM
+// PRF of the key's size; no auth key.
+void derive_session_keys_gcm(const uint8_t *mk, int key_len, const uint8_t ms[12], bool rtcp,
+                             uint8_t *enc, uint8_t salt[14]);
+
 } // namespace srtp

@@ -42,6 +42,7 @@ class SRTPPolicy:
     AESF8_ENCRYPTION = 2
     TWOFISH_ENCRYPTION = 3
     TWOFISHF8_ENCRYPTION = 4
+    AESGCM_ENCRYPTION = 5  # RFC 7714 AEAD_AES_128_GCM / AEAD_AES_256_GCM (later libjitsi's constant)
     NULL_AUTHENTICATION = 0
     HMACSHA1_AUTHENTICATION = 1
     SKEIN_AUTHENTICATION = 2
@@ -167,6 +168,12 @@ def profile_policies(profile: str):
         "TWOFISH_CM_128_SKEIN_32": (P.TWOFISH_ENCRYPTION, 16, 4),
         "TWOFISH_CM_256_SKEIN_64": (P.TWOFISH_ENCRYPTION, 32, 8),
     }
+    # RFC 7714 AEAD profiles: NULL authentication (the 16-byte tag is the
+    # cipher's own), no auth key, 12-byte salts; one policy for SRTP and SRTCP
+    gcm = {"AEAD_AES_128_GCM": 16, "AEAD_AES_256_GCM": 32}
+    if profile in gcm:
+        return (P(P.AESGCM_ENCRYPTION, gcm[profile], P.NULL_AUTHENTICATION, 0, 16, 12),
+                P(P.AESGCM_ENCRYPTION, gcm[profile], P.NULL_AUTHENTICATION, 0, 16, 12))
     if profile in skein:
         enc, klen, tag = skein[profile]
         pol = P(enc, klen, P.SKEIN_AUTHENTICATION, 32, tag, 14)
@@ -715,7 +722,9 @@ def block_encrypt(enc_type: int, key: bytes, block: bytes) -> bytes:
 
 def derive_session_keys_for(enc_type: int, masterKey: bytes, masterSalt: bytes, rtcp: bool = False):
     """Session keys with the policy's cipher as the PRF (Twofish for the ZRTP
-    Twofish policies, AES otherwise)."""
+    Twofish policies, AES otherwise).  AESGCM_ENCRYPTION: RFC 7714 11 -- a
+    12-byte master salt, a 12-byte session salt (two zero bytes follow it) and
+    a zeroed auth key."""
     mk = bytes(masterKey)
     klen = 32 if len(mk) >= 32 else 16
     enc, auth, salt = (C.c_uint8 * klen)(), (C.c_uint8 * 20)(), (C.c_uint8 * 14)()
@@ -734,6 +743,22 @@ def derive_session_keys_auth(enc_type: int, masterKey: bytes, masterSalt: bytes,
     N.check(N.lib().srtp_derive_session_keys_auth(enc_type, mk[:klen], klen, bytes(masterSalt)[:14],
                                                   int(rtcp), enc, auth, auth_len, salt), None, "kdf")
     return bytes(enc), bytes(auth), bytes(salt)
+
+
+def aes_gcm(key: bytes, iv: bytes, aad: bytes, data: bytes, tag: Optional[bytes] = None):
+    """The engine's host AES-GCM (srtp_aes_gcm; 12-byte IV, 16-byte tag).
+    Without ``tag``: seals, returns (ciphertext, tag).  With it: opens, returns
+    the plaintext, or None on a tag mismatch."""
+    assert len(iv) == 12
+    buf = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(bytes(data) or b"\0")
+    t = (C.c_uint8 * 16).from_buffer_copy(bytes(tag) if tag is not None else bytes(16))
+    rc = N.lib().srtp_aes_gcm(0 if tag is None else 1, bytes(key), len(key), bytes(iv), bytes(aad), len(aad),
+                              buf, len(data), t)
+    if rc == 1:
+        return None
+    N.check(rc, None, "aes_gcm")
+    out = bytes(buf)[:len(data)]
+    return (out, bytes(t)) if tag is None else out
 
 
 def skein512_mac(key: bytes, msg: bytes, out_bits: int = 512) -> bytes:
