@@ -78,10 +78,12 @@ extern "C" {
  * auth_key_len 0, auth_tag_len 16, salt_key_len 12}.
  * What exists for it is the host side: the key derivation of RFC 7714 11
  * (srtp_derive_session_keys_for), the AEAD itself (srtp_aes_gcm) and the
- * dispatcher's may-throw test (srtp_packet_may_throw, tag_mask bit 16).  The
- * engine has no kernel for it yet: srtp_factory_create still answers
- * SRTP_EPOLICY for such a policy, and srtp_dtls_profile_keys for the two
- * DTLS-SRTP ids (SRTP_PROFILE_AEAD_AES_*_GCM below). */
+ * dispatcher's may-throw test (srtp_packet_may_throw, tag_mask bit 16); and
+ * on the GPU the AEAD core as a stateless batch (srtp_aes_gcm_device: GHASH +
+ * AES-CTR, a lane per packet).  The engine's packet path (parse, walk, replay
+ * state) does not run it yet: srtp_factory_create still answers SRTP_EPOLICY
+ * for such a policy, and srtp_dtls_profile_keys for the two DTLS-SRTP ids
+ * (SRTP_PROFILE_AEAD_AES_*_GCM below). */
 #define SRTP_AESGCM_ENCRYPTION 5
 #define SRTP_NULL_AUTHENTICATION 0
 #define SRTP_HMACSHA1_AUTHENTICATION 1
@@ -773,6 +775,27 @@ int srtp_block_encrypt(int32_t enc_type, const uint8_t *key, int32_t key_len, co
  * 16-entry table a GPU pass would take per key set (host_crypto.h). */
 int srtp_aes_gcm(int32_t open, const uint8_t *key, int32_t key_len, const uint8_t iv[12],
                  const uint8_t *aad, int32_t aad_len, uint8_t *data, int32_t len, uint8_t tag[16]);
+
+/* The device twin of srtp_aes_gcm: n packets on the engine's device, one key
+ * (16 or 32 bytes) for the batch.  Packet i is seg[off[i] .. off[i] +
+ * aad_len[i] + len[i]), AAD first; iv holds n x 12 bytes, tag n x 16.
+ * open = 0: seal in place, write tag (result may be NULL).  open = 1:
+ * result[i] = 1 and the data left untouched on a mismatch, else 0 and
+ * deciphered.  No byte of seg outside the packets is read or written; packets
+ * must not overlap; any alignment (4-byte aligned data runs faster).  All
+ * arrays are device pointers; key is a host pointer, expanded on the host and
+ * passed in the kernel's arguments.  Enqueued on `stream` (NULL: the device's
+ * default stream); the results are ready once the stream reaches that point.
+ * Stateless: touches no factory, transformer or context of the engine, which
+ * names the device.  Like every call on an engine it holds the engine's lock
+ * while it enqueues (not while the kernel runs), so it is serialised against
+ * bundle submits from other threads on that engine, and an error's text goes
+ * to srtp_engine_last_error.  n = 0 returns SRTP_OK and launches nothing;
+ * SRTP_EINVAL for a NULL engine, key or array or a key_len other than 16 / 32. */
+int srtp_aes_gcm_device(srtp_engine *e, int32_t open, const uint8_t *key, int32_t key_len,
+                        uint8_t *seg, const uint32_t *off, const uint32_t *aad_len,
+                        const uint32_t *len, const uint8_t *iv, uint8_t *tag, int32_t *result,
+                        uint32_t n, void *stream);
 
 /* DTLS-SRTP keying (control plane, host only): what
  * DtlsPacketTransformer.initializeSRTPTransformer does after the handshake

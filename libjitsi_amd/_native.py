@@ -72,7 +72,7 @@ EXPORTED = [
     "srtp_queue_create", "srtp_queue_submit", "srtp_queue_reap", "srtp_queue_outstanding",
     "srtp_queue_aggregator", "srtp_queue_destroy", "srtp_queue_release", "srtp_packet_may_throw",
     "srtp_rawpacket_batch_set_aggregator", "srtp_rawpacket_submit", "srtp_rawpacket_complete",
-    "srtp_pipeline_query",
+    "srtp_pipeline_query", "srtp_aes_gcm_device",
 ]
 STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 
@@ -197,6 +197,7 @@ def lib() -> C.CDLL:
     L.srtp_derive_session_keys_for.argtypes = [i32, C.c_char_p, i32, C.c_char_p, i32, pu8, pu8, pu8]
     L.srtp_block_encrypt.argtypes = [i32, C.c_char_p, i32, C.c_char_p, pu8]
     L.srtp_aes_gcm.argtypes = [i32, C.c_char_p, i32, C.c_char_p, C.c_char_p, i32, pu8, i32, pu8]
+    L.srtp_aes_gcm_device.argtypes = [vp, i32, C.c_char_p, i32, vp, vp, vp, vp, vp, vp, vp, u32, vp]
     L.srtp_derive_session_keys_auth.argtypes = [i32, C.c_char_p, i32, C.c_char_p, i32, pu8, pu8, i32, pu8]
     L.srtp_skein512_mac.argtypes = [C.c_char_p, i32, i32, C.c_char_p, C.c_size_t, pu8]
     L.srtp_export_contexts.argtypes = [vp, i32, pu32, C.POINTER(CtxState), u32, pu32]

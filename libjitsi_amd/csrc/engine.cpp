@@ -1277,6 +1277,29 @@ int srtp_aes_gcm(int32_t open, const uint8_t *key, int32_t key_len, const uint8_
     return ok ? SRTP_OK : 1;
 }
 
+int srtp_aes_gcm_device(srtp_engine *e, int32_t open, const uint8_t *key, int32_t key_len,
+                        uint8_t *seg, const uint32_t *off, const uint32_t *aad_len,
+                        const uint32_t *len, const uint8_t *iv, uint8_t *tag, int32_t *result,
+                        uint32_t n, void *stream) {
+    if (!e) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> lk(e->mu);
+    const int chk = gcm_batch_check(key, key_len, seg, off, aad_len, len, iv, tag, result, open != 0, n);
+    if (chk < 0) return fail(e, SRTP_EINVAL, "a key of 16 or 32 bytes and no null buffer");
+    if (chk > 0) return SRTP_OK;
+    GUARD(e);
+    GcmBatch g{};
+    gcm_key_arg(key, key_len, &g.key);
+    g.seg = seg; g.off = off; g.aad_len = aad_len; g.len = len;
+    g.iv = iv; g.tag = tag; g.result = result;
+    g.n = n;
+    g.open = open ? 1 : 0;
+    // the launch copies the arguments, so the key block can be wiped at once
+    const hipError_t err = launch_gcm_aead(g, (hipStream_t)stream);
+    memset(&g.key, 0, sizeof g.key);
+    if (err != hipSuccess) return fail(e, SRTP_EDEVICE, std::string("k_gcm_aead: ") + hipGetErrorString(err));
+    return SRTP_OK;
+}
+
 int srtp_derive_session_keys_auth(int32_t enc_type, const uint8_t *mk, int32_t key_len,
                                   const uint8_t ms[14], int32_t rtcp, uint8_t *enc, uint8_t *auth,
                                   int32_t auth_len, uint8_t salt[14]) {

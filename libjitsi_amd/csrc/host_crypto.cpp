@@ -455,6 +455,24 @@ bool aes_gcm(bool open, const uint32_t *rk, int nr, const uint8_t iv[12], const 
     return ok;
 }
 
+void gcm_key_arg(const uint8_t *key, int key_len, GcmKeyArg *out) {
+    uint8_t h[16] = {0};
+    memset(out, 0, sizeof *out);
+    out->nr = aes_expand_le(key, key_len, out->rk);
+    aes_encrypt_block_nr(out->rk, out->nr, h, h);
+    gcm_htable(h, out->htab);
+    memset(h, 0, sizeof h);
+}
+
+int gcm_batch_check(const void *key, int key_len, const void *seg, const void *off, const void *aad_len,
+                    const void *len, const void *iv, const void *tag, const void *result, bool open,
+                    uint32_t n) {
+    if (!key || (key_len != 16 && key_len != 32)) return -1;
+    if (n == 0) return 1;
+    if (!seg || !off || !aad_len || !len || !iv || !tag || (open && !result)) return -1;
+    return 0;
+}
+
 void hmac_sha1_midstates(const uint8_t key[20], uint32_t ipad[5], uint32_t opad[5]) {
     uint8_t bi[64], bo[64];
     memset(bi, 0x36, 64);

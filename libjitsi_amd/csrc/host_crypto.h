@@ -6,6 +6,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "srtp_types.h"
+
 namespace srtp {
 
 // Expanded AES-128 encryption key, 44 words.  Word i holds round-key bytes
@@ -71,6 +73,16 @@ void gcm_mult_xor(const uint64_t tab[16][2], uint8_t y[16], const uint8_t x[16])
 // mismatch and leaves data untouched).
 bool aes_gcm(bool open, const uint32_t *rk_le, int nr, const uint8_t iv[12], const uint8_t *aad,
              size_t aad_len, uint8_t *data, size_t len, uint8_t tag[16]);
+// The key block of the stateless GPU batch (srtp_aes_gcm_device): the expanded
+// key (key_len 16 or 32) and gcm_htable(E_K(0^128)); every other byte zero.
+void gcm_key_arg(const uint8_t *key, int key_len, GcmKeyArg *out);
+// The argument rules of srtp_aes_gcm_device after its engine test: -1 for a
+// missing key or a key_len other than 16 / 32 (whatever n is); else 1 for
+// n == 0 (nothing to launch, the arrays are not looked at); else -1 when an
+// array is NULL (result only matters to open); else 0: launch.
+int gcm_batch_check(const void *key, int key_len, const void *seg, const void *off, const void *aad_len,
+                    const void *len, const void *iv, const void *tag, const void *result, bool open,
+                    uint32_t n);
 // RFC 7714 11: the session encryption key (key_len bytes) and the 12-byte
 // session salt (salt[12..13] = 0) from a 12-byte master salt, by the AES-CM
 // PRF of the key's size; no auth key.

@@ -177,6 +177,20 @@ hipError_t launch_rehash_collect(const uint64_t *ctx_keys, const CtxState *ctx, 
 hipError_t launch_rehash_insert(uint64_t *ctx_keys, CtxState *ctx, uint32_t mask,
                                 const uint64_t *tmp_keys, const CtxState *tmp_ctx, uint32_t n,
                                 hipStream_t s);
+// srtp_aes_gcm_device: one stateless AES-GCM batch under one key (k_gcm_aead).
+// The key travels by value in the kernel arguments (GcmKeyArg, srtp_types.h).
+struct GcmBatch {
+    GcmKeyArg key;
+    uint8_t *seg;
+    const uint32_t *off, *aad_len, *len; // [n] packet i: seg[off[i], + aad_len[i] + len[i]), AAD first
+    const uint8_t *iv;                   // [n][12]
+    uint8_t *tag;                        // [n][16]
+    int32_t *result;                     // [n] open: 1 on a tag mismatch (data untouched), else 0
+    uint32_t n;
+    int32_t open;
+};
+// n > 0; needs upload_tables() on the current device (every engine does it)
+hipError_t launch_gcm_aead(const GcmBatch &g, hipStream_t s);
 // Upload the LE T-table used by the AES rounds (once per device).
 hipError_t upload_tables(const uint32_t te0[256]);
 

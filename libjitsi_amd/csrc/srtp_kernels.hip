@@ -27,6 +27,11 @@
 //   k_unprotect_fix [unprotect] statuses/lengths out; undoes/redoes the rare
 //              packets whose speculation the walk overturned.
 //
+// Outside the bundle pipeline:
+//   k_gcm_aead [srtp_aes_gcm_device] AES-GCM of a batch of packets under one
+//              key, a lane per packet (GHASH by a 4-bit table in LDS + AES-CTR);
+//              stateless, launched by no bundle.
+//
 // AES uses four little-endian T-tables replicated 32x in LDS (128 KB) so that
 // lane l only ever touches LDS bank (l & 31): conflict-free ds_read_b32 with a
 // single v_perm_b32 per lookup address and v_bitop3 XORs.  Round keys, salt
@@ -4555,6 +4560,232 @@ __global__ __launch_bounds__(kSkeinBlock) void k_skein(BundleArgs a) {
     });
 }
 
+// ============================================================== AES-GCM
+// NIST SP 800-38D with a 96-bit IV and a 16-byte tag, as RFC 7714 uses it; a
+// lane takes one packet (the simple form: GHASH is a serial chain per packet).
+//
+// GHASH is Shoup's 4-bit method against the key's table (GcmKeyArg::htab, from
+// the host's gcm_htable) staged in LDS: 16 entries x 16 B are one 256-B bank
+// row, so a ds_read_b128 wave instruction whose lanes read different entries
+// has no bank conflict and lanes reading the same entry broadcast.  One
+// multiplication is 32 such reads and 31 shifts by four bits, each with the
+// reduction of the nibble shifted out (16 bits, computed: a carry-less
+// product with 0x1c20).
+constexpr int kGcmBlock = 1024;     // at most: 16 waves around one T-table image
+constexpr int kGcmTabWords = 64;    // one key's table in LDS, after the image
+
+// Z = (Z ^ X) * H; halves in the field's big-endian bit order, as on the host
+// (host_crypto.cpp gcm_mult_xor).  tab: the key's table in LDS.
+__device__ __forceinline__ void gcm_mult_xor(const uint32_t *tab, uint64_t &zh, uint64_t &zl, uint64_t xh,
+                                             uint64_t xl) {
+    const uint64_t v[2] = {xl ^ zl, xh ^ zh};
+    uint64_t h = 0ull, l = 0ull;
+#pragma unroll
+    for (int half = 0; half < 2; half++) { // nibbles from the last byte's low one up
+        const uint64_t x = v[half];
+#pragma unroll 4
+        for (int k = 0; k < 16; k++) {
+            if (half | k) {
+                const uint32_t rem = (uint32_t)l & 15u;
+                l = (h << 60) | (l >> 4);
+                h = (h >> 4) ^ ((uint64_t)((rem << 5) ^ (rem << 10) ^ (rem << 11) ^ (rem << 12)) << 48);
+            }
+            const uint32_t nib = (uint32_t)(x >> (4 * k)) & 15u;
+            const uint4 e = *reinterpret_cast<const uint4 *>(tab + 4u * nib);
+            l ^= (uint64_t)e.x | ((uint64_t)e.y << 32);
+            h ^= (uint64_t)e.z | ((uint64_t)e.w << 32);
+        }
+    }
+    zh = h;
+    zl = l;
+}
+
+// One GHASH step with the block held as four little-endian words.
+__device__ __forceinline__ void gcm_absorb(const uint32_t *tab, uint64_t &zh, uint64_t &zl,
+                                           const uint32_t w[4]) {
+    gcm_mult_xor(tab, zh, zl, ((uint64_t)bswap(w[0]) << 32) | bswap(w[1]),
+                 ((uint64_t)bswap(w[2]) << 32) | bswap(w[3]));
+}
+
+// Bytes [0, m) of p (1 <= m <= 16) as four little-endian words, zero-padded;
+// no byte at or after p + m is read.
+__device__ __forceinline__ void gcm_load(const uint8_t *p, int m, uint32_t w[4]) {
+    if (m >= 16 && (reinterpret_cast<uintptr_t>(p) & 3u) == 0u) {
+        const uint32_t *q = reinterpret_cast<const uint32_t *>(p);
+#pragma unroll
+        for (int k = 0; k < 4; k++) w[k] = q[k];
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        uint32_t x = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if (4 * k + i < m) x |= ld_u8(p + 4 * k + i) << (8 * i);
+        w[k] = x;
+    }
+}
+
+// ... and back: only bytes [0, m) of p are written.
+__device__ __forceinline__ void gcm_store(uint8_t *p, int m, const uint32_t w[4]) {
+    if (m >= 16 && (reinterpret_cast<uintptr_t>(p) & 3u) == 0u) {
+        uint32_t *q = reinterpret_cast<uint32_t *>(p);
+#pragma unroll
+        for (int k = 0; k < 4; k++) q[k] = w[k];
+        return;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if (4 * k + i < m) p[4 * k + i] = (uint8_t)(w[k] >> (8 * i));
+}
+
+// GHASH of bytes [0, n) of p, zero-padded to whole blocks.
+__device__ __forceinline__ void gcm_absorb_bytes(const uint32_t *tab, uint64_t &zh, uint64_t &zl,
+                                                 const uint8_t *p, int n) {
+    for (int o = 0; o < n; o += 16) {
+        uint32_t w[4];
+        gcm_load(p + o, min(16, n - o), w);
+        gcm_absorb(tab, zh, zl, w);
+    }
+}
+
+// One packet: AAD at aad[0, aad_len), the data right behind it, len bytes.
+struct GcmPkt {
+    uint8_t *aad;
+    int aad_len, len;
+    uint32_t iv[3]; // the 12 IV bytes as little-endian words
+};
+
+enum { kGcmSeal = 0, kGcmVerify = 1, kGcmDecipher = 2 };
+
+// The whole AEAD for one lane's packet, in one of three modes:
+//   seal      AES-CTR (inc32 from counter 2) over the data in place, GHASH over
+//             AAD || ciphertext || lengths, tag = GHASH ^ E_K(IV || 1);
+//   verify    that tag over the data as it stands (ciphertext), nothing written;
+//   decipher  the AES-CTR pass alone (tag[] untouched).
+// tag[]: the 16 tag bytes as little-endian words.  Cipher: encrypt2() of two
+// blocks, as k_ext's ciphers; the mask block E_K(IV || 1) shares the first
+// pair with counter 2.  Touches no byte outside [aad, aad + aad_len + len).
+template <int MODE, class Cipher>
+__device__ __forceinline__ void gcm_packet(const Cipher &cipher, const uint32_t *tab, const GcmPkt &j,
+                                           uint32_t tag[4]) {
+    uint8_t *data = j.aad + j.aad_len;
+    const int nb = (j.len + 15) >> 4;
+    uint64_t zh = 0ull, zl = 0ull;
+    uint32_t mask[4] = {0u, 0u, 0u, 0u};
+    if (MODE != kGcmDecipher) gcm_absorb_bytes(tab, zh, zl, j.aad, j.aad_len);
+    if (MODE == kGcmVerify) gcm_absorb_bytes(tab, zh, zl, data, j.len);
+    // counter blocks in pairs: c, c + 1; counter c ciphers data block c - 2
+    for (int c = MODE == kGcmDecipher ? 2 : 1; c == 1 || c - 2 < nb; c += 2) {
+        uint32_t x[4] = {j.iv[0], j.iv[1], j.iv[2], bswap((uint32_t)c)};
+        uint32_t y[4] = {j.iv[0], j.iv[1], j.iv[2], bswap((uint32_t)c + 1u)};
+        cipher.encrypt2(x, y);
+        if (MODE == kGcmVerify) { // only the mask block is wanted
+#pragma unroll
+            for (int k = 0; k < 4; k++) mask[k] = x[k];
+            break;
+        }
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const uint32_t *ks = u ? y : x;
+            const int b = c - 2 + u;
+            if (b < 0) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) mask[k] = ks[k];
+            } else if (b < nb) {
+                const int m = min(16, j.len - 16 * b);
+                uint32_t d[4];
+                gcm_load(data + 16 * b, m, d);
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int keep = m - 4 * k; // bytes of word k inside the data
+                    const uint32_t km = keep >= 4 ? ~0u : (keep <= 0 ? 0u : (1u << (8 * keep)) - 1u);
+                    d[k] = (d[k] ^ ks[k]) & km;
+                }
+                gcm_store(data + 16 * b, m, d);
+                if (MODE == kGcmSeal) gcm_absorb(tab, zh, zl, d);
+            }
+        }
+    }
+    if (MODE == kGcmDecipher) return;
+    gcm_mult_xor(tab, zh, zl, (uint64_t)j.aad_len * 8ull, (uint64_t)j.len * 8ull);
+    tag[0] = bswap((uint32_t)(zh >> 32)) ^ mask[0];
+    tag[1] = bswap((uint32_t)zh) ^ mask[1];
+    tag[2] = bswap((uint32_t)(zl >> 32)) ^ mask[2];
+    tag[3] = bswap((uint32_t)zl) ^ mask[3];
+}
+
+// AES-128 or AES-256 under round keys held in SGPRs for the whole kernel (one
+// key per launch: srtp_aes_gcm_device's batch).
+struct GcmBatchCipher {
+    const char *lds;
+    TeBase tb;
+    const RoundKeys256 &rk;
+    bool a256;
+    __device__ __forceinline__ void encrypt2(uint32_t a[4], uint32_t b[4]) const {
+        if (a256) {
+            aes256_encrypt2(lds, tb, rk, a, b);
+        } else {
+            RoundKeys r;
+#pragma unroll
+            for (int i = 0; i < 44; i++) r.k[i] = rk.k[i];
+            aes_encrypt2(lds, tb, r, a, b);
+        }
+    }
+};
+
+// ============================================================== k_gcm_aead
+// The stateless batch (srtp_aes_gcm_device): n packets under one key, which
+// travels in the kernel arguments -- round keys straight into SGPRs, the GHASH
+// table into LDS -- so the call owns no device memory and calls on different
+// streams share nothing.
+__global__ __launch_bounds__(kGcmBlock) void k_gcm_aead(GcmBatch g) {
+    __shared__ uint32_t s_te[kTeWords + kGcmTabWords]; // the image stays at LDS 0
+    if (threadIdx.x < (unsigned)kGcmTabWords) {
+        // word threadIdx.x of the table: the argument words are scalars, so a
+        // lane selects its own (once per workgroup)
+        uint32_t v = 0u;
+#pragma unroll
+        for (int i = 0; i < kGcmTabWords; i++) {
+            const uint32_t wi = (uint32_t)(g.key.htab[i >> 2][(i >> 1) & 1] >> (32 * (i & 1)));
+            v = threadIdx.x == (unsigned)i ? wi : v;
+        }
+        s_te[kTeWords + threadIdx.x] = v;
+    }
+    fill_te4(s_te); // ends with a barrier: the table above is visible too
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= g.n) return;
+    const uint32_t *tab = s_te + kTeWords;
+    RoundKeys256 rk;
+#pragma unroll
+    for (int k = 0; k < 60; k++) rk.k[k] = sgpr(g.key.rk[k]);
+    const GcmBatchCipher cipher{reinterpret_cast<const char *>(s_te), te_base(), rk, sgpr((uint32_t)g.key.nr) == 14u};
+    GcmPkt j;
+    j.aad = g.seg + g.off[i];
+    j.aad_len = (int)g.aad_len[i];
+    j.len = (int)g.len[i];
+    const uint8_t *ivp = g.iv + 12 * (size_t)i;
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+        j.iv[k] = ld_u8(ivp + 4 * k) | (ld_u8(ivp + 4 * k + 1) << 8) | (ld_u8(ivp + 4 * k + 2) << 16) |
+                  (ld_u8(ivp + 4 * k + 3) << 24);
+    uint8_t *tagp = g.tag + 16 * (size_t)i;
+    uint32_t tag[4];
+    if (!g.open) {
+        gcm_packet<kGcmSeal>(cipher, tab, j, tag);
+        gcm_store(tagp, 16, tag);
+        return;
+    }
+    uint32_t got[4];
+    gcm_packet<kGcmVerify>(cipher, tab, j, tag);
+    gcm_load(tagp, 16, got);
+    const bool ok = ((tag[0] ^ got[0]) | (tag[1] ^ got[1]) | (tag[2] ^ got[2]) | (tag[3] ^ got[3])) == 0u;
+    g.result[i] = ok ? 0 : 1;
+    if (ok) gcm_packet<kGcmDecipher>(cipher, tab, j, tag);
+}
+
 // ============================================================== maintenance
 __global__ void k_remove_transformer(uint64_t *keys, CtxState *ctx, uint32_t cap, uint32_t tid) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -4695,6 +4926,11 @@ hipError_t launch_unprotect(const BundleArgs &a, hipStream_t s) {
 }
 hipError_t launch_skein(const BundleArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(k_skein, dim3((a.n + kSkeinBlock - 1) / kSkeinBlock), dim3(kSkeinBlock), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t launch_gcm_aead(const GcmBatch &g, hipStream_t s) {
+    const uint32_t b = aes_block(g.n, (uint32_t)kGcmBlock);
+    hipLaunchKernelGGL(k_gcm_aead, dim3((g.n + b - 1) / b), dim3(b), 0, s, g);
     return hipGetLastError();
 }
 

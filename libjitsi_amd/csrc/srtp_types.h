@@ -63,6 +63,17 @@ struct alignas(64) SkeinKeys {
 };
 static_assert(sizeof(SkeinKeys) == 64, "SkeinKeys is 64 B");
 
+// One AES-GCM key as the stateless batch kernel takes it (k_gcm_aead), by
+// value in its arguments: the expanded AES key and the GHASH table of Shoup's
+// 4-bit method (host_crypto.h gcm_key_arg).
+struct GcmKeyArg {
+    uint32_t rk[60];      // 4 * (nr + 1) round-key words, little-endian column words; the rest 0
+    int32_t nr;           // 10 or 14
+    uint32_t pad[3];
+    uint64_t htab[16][2]; // gcm_htable(E_K(0^128)): {low, high} halves of i * H
+};
+static_assert(sizeof(GcmKeyArg) == 512, "GcmKeyArg is 512 B");
+
 struct FactoryRec {      // SRTPContextFactory
     int32_t open;        // 0 after close(): getDefaultContext() == null
     int32_t ks_rtp;      // key set of its default SRTPCryptoContext

@@ -761,6 +761,36 @@ def aes_gcm(key: bytes, iv: bytes, aad: bytes, data: bytes, tag: Optional[bytes]
     return (out, bytes(t)) if tag is None else out
 
 
+def aes_gcm_device(engine, key: bytes, seg, off, aad_len, length, iv, tag, result=None,
+                   open: bool = False, n: Optional[int] = None, stream=None) -> None:
+    """AES-GCM on the GPU for a batch of packets under one key
+    (srtp_aes_gcm_device): the device twin of :func:`aes_gcm`.  All buffers are
+    torch tensors on ``engine``'s GPU: packet i is ``seg[off[i] : off[i] +
+    aad_len[i] + length[i]]`` (uint8; AAD first), ``off`` / ``aad_len`` /
+    ``length`` uint32-sized ints (int32 tensors), ``iv`` n x 12 and ``tag``
+    n x 16 bytes.  Seals in place and writes ``tag``; with ``open`` it checks
+    ``tag`` instead: ``result[i]`` (int32) is 1 and the data untouched on a
+    mismatch, else 0 and the data deciphered.  Async on ``stream`` like
+    :meth:`SRTPEngine.transform_device`; touches none of the engine's state."""
+    if n is None:
+        n = off.numel()
+    for t, size, what in ((off, 4, "off"), (aad_len, 4, "aad_len"), (length, 4, "length"),
+                          (iv, 1, "iv"), (tag, 1, "tag"), (seg, 1, "seg")) + \
+            (((result, 4, "result"),) if result is not None else ()):
+        if t.element_size() != size or not t.is_contiguous():
+            raise ValueError("%s: a contiguous tensor of %d-byte elements" % (what, size))
+    if off.numel() < n or aad_len.numel() < n or length.numel() < n or iv.numel() < 12 * n or \
+            tag.numel() < 16 * n or (result is not None and result.numel() < n):
+        raise ValueError("an array is shorter than n packets")
+    if open and result is None and n:
+        raise ValueError("open needs a result tensor")
+    sp = getattr(stream, "cuda_stream", stream)
+    rc = N.lib().srtp_aes_gcm_device(
+        engine.h, int(bool(open)), bytes(key), len(key), seg.data_ptr(), off.data_ptr(), aad_len.data_ptr(),
+        length.data_ptr(), iv.data_ptr(), tag.data_ptr(), None if result is None else result.data_ptr(), n, sp)
+    N.check(rc, engine.h, "srtp_aes_gcm_device")
+
+
 def skein512_mac(key: bytes, msg: bytes, out_bits: int = 512) -> bytes:
     """The engine's host Skein-512 (version 1.3): keyed like bccontrib's SkeinMac
     (plain hash for an empty key), out_bits output bits."""

@@ -85,6 +85,50 @@ int main() {
             srtp::derive_session_keys_n(mk.data(), klen, ms14, rtcp != 0, enc2.data(), auth, salt2);
             CHECK(enc == enc2 && memcmp(salt, salt2, 12) == 0 && salt[12] == 0 && salt[13] == 0);
         }
+    // the GPU batch's key block (srtp_aes_gcm_device): the key schedule and
+    // table aes_gcm itself uses, nr, and zero everywhere else, written into
+    // an exact-size heap object
+    for (int klen : {16, 32}) {
+        std::vector<uint8_t> key((size_t)klen);
+        for (auto &b : key) b = rnd();
+        std::vector<srtp::GcmKeyArg> ka(1);
+        memset((void *)ka.data(), 0xff, sizeof(srtp::GcmKeyArg));
+        srtp::gcm_key_arg(key.data(), klen, ka.data());
+        uint32_t rk[60] = {0};
+        uint64_t tab[16][2];
+        uint8_t h[16] = {0};
+        const int nr = srtp::aes_expand_le(key.data(), klen, rk);
+        srtp::aes_encrypt_block_nr(rk, nr, h, h);
+        srtp::gcm_htable(h, tab);
+        CHECK(ka[0].nr == nr && nr == (klen == 16 ? 10 : 14));
+        CHECK(memcmp(ka[0].rk, rk, sizeof rk) == 0);
+        CHECK(memcmp(ka[0].htab, tab, sizeof tab) == 0);
+        CHECK(ka[0].pad[0] == 0 && ka[0].pad[1] == 0 && ka[0].pad[2] == 0);
+        // one multiplication by hand: (0 ^ x^0) * H = H, the table's entry 8
+        uint8_t y[16] = {0}, one[16] = {0x80};
+        srtp::gcm_mult_xor(ka[0].htab, y, one);
+        CHECK(memcmp(y, h, 16) == 0);
+    }
+    // srtp_aes_gcm_device's argument rules (the key test comes before n == 0)
+    {
+        const uint8_t k[32] = {0};
+        int x = 0;
+        const void *p = &x;
+        CHECK(srtp::gcm_batch_check(k, 16, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, 0) == 1);
+        CHECK(srtp::gcm_batch_check(k, 32, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, 0) == 1);
+        CHECK(srtp::gcm_batch_check(k, 24, p, p, p, p, p, p, p, false, 0) == -1);
+        CHECK(srtp::gcm_batch_check(k, 24, p, p, p, p, p, p, p, false, 1) == -1);
+        CHECK(srtp::gcm_batch_check(nullptr, 16, p, p, p, p, p, p, p, false, 1) == -1);
+        CHECK(srtp::gcm_batch_check(k, 16, p, p, p, p, p, p, nullptr, false, 1) == 0);
+        CHECK(srtp::gcm_batch_check(k, 16, p, p, p, p, p, p, nullptr, true, 1) == -1);
+        CHECK(srtp::gcm_batch_check(k, 32, p, p, p, p, p, p, p, true, 1u << 31) == 0);
+        const void *a[6] = {p, p, p, p, p, p};
+        for (int i = 0; i < 6; i++) {
+            a[i] = nullptr;
+            CHECK(srtp::gcm_batch_check(k, 16, a[0], a[1], a[2], a[3], a[4], a[5], p, true, 1) == -1);
+            a[i] = p;
+        }
+    }
     printf(failures ? "gcm_host_check: %d failures\n" : "gcm_host_check: ok\n", failures);
     return failures ? 1 : 0;
 }
