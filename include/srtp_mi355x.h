@@ -76,14 +76,20 @@ extern "C" {
  * later libjitsi's SRTPPolicy.AESGCM_ENCRYPTION).  The policy shape is
  * {SRTP_AESGCM_ENCRYPTION, enc_key_len 16 or 32, SRTP_NULL_AUTHENTICATION,
  * auth_key_len 0, auth_tag_len 16, salt_key_len 12}.
- * What exists for it is the host side: the key derivation of RFC 7714 11
- * (srtp_derive_session_keys_for), the AEAD itself (srtp_aes_gcm) and the
- * dispatcher's may-throw test (srtp_packet_may_throw, tag_mask bit 16); and
- * on the GPU the AEAD core as a stateless batch (srtp_aes_gcm_device: GHASH +
- * AES-CTR, a lane per packet).  The engine's packet path (parse, walk, replay
- * state) does not run it yet: srtp_factory_create still answers SRTP_EPOLICY
- * for such a policy, and srtp_dtls_profile_keys for the two DTLS-SRTP ids
- * (SRTP_PROFILE_AEAD_AES_*_GCM below). */
+ * The engine's packet path runs it behind a per-engine switch,
+ * srtp_engine_enable_aead (off on a new engine: srtp_factory_create then
+ * answers SRTP_EPOLICY for such a policy, as for any other GCM-typed shape
+ * with the switch on).  Either policy of a factory, or both, may be GCM.
+ * Packets: SRTP header as AAD, ciphertext, 16-byte tag; SRTCP header(8),
+ * ciphertext, tag, E|index word, the word being AAD too (RFC 7714 8-9;
+ * statuses and lengths in srtp_gcm_packet_job).  Bundles only
+ * (srtp_transform_*, srtp_pipeline_*, srtp_dispatch_*): the per-packet paths
+ * (srtp_aggregator_*, srtp_queue_*, srtp_rawpacket_*) leave 16 bytes of trailer
+ * room, four short of GCM SRTCP.  Beside it: the key derivation of RFC 7714 11
+ * (srtp_derive_session_keys_for), the AEAD on the host (srtp_aes_gcm) and as a
+ * stateless GPU batch (srtp_aes_gcm_device), the dispatcher's may-throw test
+ * (srtp_packet_may_throw, tag_mask bit 16), and the DTLS-SRTP ids
+ * SRTP_PROFILE_AEAD_AES_*_GCM through srtp_dtls_profile_keys_ex. */
 #define SRTP_AESGCM_ENCRYPTION 5
 #define SRTP_NULL_AUTHENTICATION 0
 #define SRTP_HMACSHA1_AUTHENTICATION 1
@@ -253,6 +259,12 @@ int srtp_engine_stats(srtp_engine *e, srtp_stats *out);
  * FORCE_WIDE and NO_WIDE keep them off it too. */
 #define SRTP_DEBUG_NO_SMALL 0x8u
 int srtp_engine_set_debug(srtp_engine *e, uint32_t flags);
+/* The AES-GCM switch (RFC 7714 profiles, see SRTP_AESGCM_ENCRYPTION): off on a
+ * new engine.  While on, srtp_factory_create accepts the GCM policy shape for
+ * its SRTP and / or SRTCP policy; turning it off again refuses new such
+ * factories and leaves existing ones working.  An engine that holds a GCM
+ * factory runs every bundle on the multi-kernel path. */
+int srtp_engine_enable_aead(srtp_engine *e, int32_t on);
 
 /* Context-state export / import: lets a stream's ROC, s_l,
  * replay window and SRTCP indices follow it to another engine or GPU (SSRC
@@ -585,6 +597,8 @@ void srtp_dispatch_destroy(srtp_dispatch *d);
 const char *srtp_dispatch_last_error(srtp_dispatch *d);
 int32_t srtp_dispatch_num_shards(srtp_dispatch *d);
 srtp_engine *srtp_dispatch_engine(srtp_dispatch *d, int32_t shard);
+/* srtp_engine_enable_aead on every shard's engine */
+int srtp_dispatch_enable_aead(srtp_dispatch *d, int32_t on);
 int srtp_dispatch_factory_create(srtp_dispatch *d, int32_t sender, const uint8_t *master_key,
                                  int32_t key_len, const uint8_t *master_salt, int32_t salt_len,
                                  const srtp_policy *srtp, const srtp_policy *srtcp, int32_t *out);
@@ -797,6 +811,26 @@ int srtp_aes_gcm_device(srtp_engine *e, int32_t open, const uint8_t *key, int32_
                         const uint32_t *len, const uint8_t *iv, uint8_t *tag, int32_t *result,
                         uint32_t n, void *stream);
 
+/* The stateless geometry of one packet under the AES-GCM profiles (host only;
+ * the function the GPU passes take every offset from): the status the lengths
+ * alone decide (`status`, -1: none), else the head AAD [0, aad_len), the
+ * E|index word's place (word_at, -1: none; word_aad: it is AAD too, behind the
+ * head AAD; unprotect reads it there, protect writes it), the data
+ * [data_at, data_at + data_len), the tag [tag_at, tag_at + 16) and the length
+ * the packet leaves with (new_len; under an early status, the length
+ * reported).  A range is handed out only inside [0, cap).  header_len: the RTP
+ * header length or SRTP_GCM_HDR_THROW (ignored for SRTCP); e_bit: SRTCP
+ * unprotect, the word's E bit (word_at does not depend on it); decipher: 0 for
+ * an SRTP unprotect flagged DISCARD / SILENCE.  Stateful checks lie between:
+ * ERR_CAPACITY precedes every state change, SRTP's replay check precedes its
+ * ERR_MALFORMED / DROP_AUTH, SRTCP's follows them. */
+#define SRTP_GCM_HDR_THROW ((int32_t)0x80000000)
+typedef struct {
+    int32_t status, new_len, aad_len, word_at, word_aad, data_at, data_len, tag_at, decipher;
+} srtp_gcm_job;
+int srtp_gcm_packet_job(int32_t kind, int32_t reverse, int32_t len, int32_t cap, int32_t header_len,
+                        uint32_t flags, int32_t e_bit, srtp_gcm_job *out);
+
 /* DTLS-SRTP keying (control plane, host only): what
  * DtlsPacketTransformer.initializeSRTPTransformer does after the handshake
  * (transform/dtls/DtlsPacketTransformer.java:549-690).
@@ -829,8 +863,12 @@ int srtp_aes_gcm_device(srtp_engine *e, int32_t open, const uint8_t *key, int32_
 #define SRTP_PROFILE_AES128_CM_HMAC_SHA1_32 0x0002
 #define SRTP_PROFILE_NULL_HMAC_SHA1_80 0x0005
 #define SRTP_PROFILE_NULL_HMAC_SHA1_32 0x0006
-/* RFC 7714 14.2 (16- / 32-byte key, 12-byte salt, 16-byte tag): the ids only;
- * srtp_dtls_profile_keys does not know them until the engine runs AES-GCM */
+/* RFC 7714 14.2 (16- / 32-byte key, 12-byte salt, 16-byte tag).
+ * srtp_dtls_profile_keys answers SRTP_EPOLICY for them, as it always has;
+ * srtp_dtls_profile_keys_ex with SRTP_DTLS_AEAD knows them: both policies the
+ * GCM shape, keying_material_len = 2 * (key + 12), the same client key |
+ * server key | client salt | server salt split (RFC 5764 4.2).  Without the
+ * flag it is srtp_dtls_profile_keys with wider key fields. */
 #define SRTP_PROFILE_AEAD_AES_128_GCM 0x0007
 #define SRTP_PROFILE_AEAD_AES_256_GCM 0x0008
 #define SRTP_TLS_PRF_TLS10 0
@@ -846,6 +884,15 @@ int srtp_tls_export_keying_material(int32_t prf, const uint8_t *master_secret, i
                                     const uint8_t client_random[32], const uint8_t server_random[32],
                                     const char *label, uint8_t *out, int32_t out_len);
 int srtp_dtls_profile_keys(int32_t profile, const uint8_t *km, int32_t km_len, srtp_dtls_keys *out);
+#define SRTP_DTLS_AEAD 0x1u
+typedef struct {
+    srtp_policy srtp, srtcp;
+    int32_t key_len, salt_len, keying_material_len;
+    uint8_t client_key[32], server_key[32];
+    uint8_t client_salt[14], server_salt[14];
+} srtp_dtls_keys_ex;
+int srtp_dtls_profile_keys_ex(int32_t profile, const uint8_t *km, int32_t km_len, srtp_dtls_keys_ex *out,
+                              uint32_t flags);
 int srtp_dtls_transformer_create(srtp_engine *e, int32_t profile, int32_t is_client, int32_t kind,
                                  const uint8_t *km, int32_t km_len, int32_t *out_transformer,
                                  int32_t out_factories[2]);

@@ -73,13 +73,16 @@ EXPORTED = [
     "srtp_queue_aggregator", "srtp_queue_destroy", "srtp_queue_release", "srtp_packet_may_throw",
     "srtp_rawpacket_batch_set_aggregator", "srtp_rawpacket_submit", "srtp_rawpacket_complete",
     "srtp_pipeline_query", "srtp_aes_gcm_device",
+    "srtp_engine_enable_aead", "srtp_gcm_packet_job", "srtp_dtls_profile_keys_ex",
+    "srtp_dispatch_enable_aead",
 ]
 STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 
 
 # Sources that decide what the crypto kernels execute: the key that ties
 # committed PMC counters (profiles/pmc_traffic.json) to the build they measured.
-KERNEL_SOURCES = ["srtp_kernels.hip", "aes_rounds_asm.inc", "srtp_kernels.h", "srtp_types.h", "engine.cpp"]
+KERNEL_SOURCES = ["srtp_kernels.hip", "aes_rounds_asm.inc", "srtp_kernels.h", "srtp_types.h", "engine.cpp",
+                  "gcm_job.h"]
 
 
 def kernel_source_sha16() -> str:
@@ -134,6 +137,24 @@ class DtlsKeys(C.Structure):
                 ("salt_len", C.c_int32), ("keying_material_len", C.c_int32),
                 ("client_key", C.c_uint8 * 16), ("server_key", C.c_uint8 * 16),
                 ("client_salt", C.c_uint8 * 14), ("server_salt", C.c_uint8 * 14)]
+
+
+class DtlsKeysEx(C.Structure):
+    """srtp_dtls_keys_ex (include/srtp_mi355x.h): room for 32-byte keys"""
+    _fields_ = [("srtp", Policy), ("srtcp", Policy), ("key_len", C.c_int32),
+                ("salt_len", C.c_int32), ("keying_material_len", C.c_int32),
+                ("client_key", C.c_uint8 * 32), ("server_key", C.c_uint8 * 32),
+                ("client_salt", C.c_uint8 * 14), ("server_salt", C.c_uint8 * 14)]
+
+
+class GcmJob(C.Structure):
+    """srtp_gcm_job (include/srtp_mi355x.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("status", "new_len", "aad_len", "word_at", "word_aad",
+                                         "data_at", "data_len", "tag_at", "decipher")]
+
+
+DTLS_AEAD = 0x1
+GCM_HDR_THROW = -0x80000000
 
 
 class AggregatorOpts(C.Structure):
@@ -250,6 +271,10 @@ def lib() -> C.CDLL:
     L.srtp_tls_export_keying_material.argtypes = [i32, C.c_char_p, i32, C.c_char_p, C.c_char_p,
                                                   C.c_char_p, vp, i32]
     L.srtp_dtls_profile_keys.argtypes = [i32, C.c_char_p, i32, C.POINTER(DtlsKeys)]
+    L.srtp_dtls_profile_keys_ex.argtypes = [i32, C.c_char_p, i32, C.POINTER(DtlsKeysEx), u32]
+    L.srtp_engine_enable_aead.argtypes = [vp, i32]
+    L.srtp_dispatch_enable_aead.argtypes = [vp, i32]
+    L.srtp_gcm_packet_job.argtypes = [i32, i32, i32, i32, i32, u32, i32, C.POINTER(GcmJob)]
     L.srtp_dtls_transformer_create.argtypes = [vp, i32, i32, i32, C.c_char_p, i32, pi32, pi32]
     L.srtp_engine_stream.argtypes = [vp]
     L.srtp_engine_stream.restype = vp

@@ -735,6 +735,12 @@ int srtp_dispatch_factory_create(srtp_dispatch *d, int32_t sender, const uint8_t
     return SRTP_OK;
 }
 
+int srtp_dispatch_enable_aead(srtp_dispatch *d, int32_t on) {
+    if (!d) return SRTP_EINVAL;
+    std::lock_guard<FairMutex> g(d->mu);
+    return each(d, [&](srtp_engine *e) { return srtp_engine_enable_aead(e, on); });
+}
+
 int srtp_dispatch_factory_close(srtp_dispatch *d, int32_t factory) {
     if (!d) return SRTP_EINVAL;
     std::lock_guard<FairMutex> g(d->mu);

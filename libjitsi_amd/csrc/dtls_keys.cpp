@@ -231,6 +231,47 @@ int srtp_dtls_profile_keys(int32_t profile, const uint8_t *km, int32_t km_len, s
     return SRTP_OK;
 }
 
+int srtp_dtls_profile_keys_ex(int32_t profile, const uint8_t *km, int32_t km_len, srtp_dtls_keys_ex *out,
+                              uint32_t flags) {
+    if (!out) return SRTP_EINVAL;
+    const bool aead = (flags & SRTP_DTLS_AEAD) &&
+                      (profile == SRTP_PROFILE_AEAD_AES_128_GCM || profile == SRTP_PROFILE_AEAD_AES_256_GCM);
+    if (!aead) { // the old table, into the wider record
+        srtp_dtls_keys k;
+        const int rc = srtp_dtls_profile_keys(profile, km, km_len, &k);
+        if (rc != SRTP_OK) return rc;
+        memset(out, 0, sizeof *out);
+        out->srtp = k.srtp;
+        out->srtcp = k.srtcp;
+        out->key_len = k.key_len;
+        out->salt_len = k.salt_len;
+        out->keying_material_len = k.keying_material_len;
+        memcpy(out->client_key, k.client_key, sizeof k.client_key);
+        memcpy(out->server_key, k.server_key, sizeof k.server_key);
+        memcpy(out->client_salt, k.client_salt, sizeof k.client_salt);
+        memcpy(out->server_salt, k.server_salt, sizeof k.server_salt);
+        memset(&k, 0, sizeof k);
+        return SRTP_OK;
+    }
+    // RFC 7714 14.2: AEAD_AES_128_GCM / AEAD_AES_256_GCM, 12-byte salt, 16-byte tag
+    const int32_t klen = profile == SRTP_PROFILE_AEAD_AES_128_GCM ? 16 : 32, slen = 12;
+    memset(out, 0, sizeof *out);
+    out->key_len = klen;
+    out->salt_len = slen;
+    out->keying_material_len = 2 * (klen + slen);
+    const srtp_policy pol = {SRTP_AESGCM_ENCRYPTION, klen, SRTP_NULL_AUTHENTICATION, 0, 16, slen};
+    out->srtp = pol;
+    out->srtcp = pol;
+    if (!km) return SRTP_OK;
+    if (km_len < out->keying_material_len) return SRTP_EINVAL;
+    const uint8_t *q = km; // client key | server key | client salt | server salt (RFC 5764 4.2)
+    memcpy(out->client_key, q, (size_t)klen); q += klen;
+    memcpy(out->server_key, q, (size_t)klen); q += klen;
+    memcpy(out->client_salt, q, (size_t)slen); q += slen;
+    memcpy(out->server_salt, q, (size_t)slen);
+    return SRTP_OK;
+}
+
 int srtp_dtls_transformer_create(srtp_engine *e, int32_t profile, int32_t is_client, int32_t kind,
                                  const uint8_t *km, int32_t km_len, int32_t *out_transformer,
                                  int32_t out_factories[2]) {

@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include "../../include/srtp_mi355x.h"
+#include "gcm_job.h"
 #include "host_crypto.h"
 #include "srtp_kernels.h"
 
@@ -35,6 +36,9 @@ struct srtp_engine {
     SkeinKeys *d_skkeys = nullptr;   // 1 per key set, allocated with the first Skein factory
     uint32_t n_ext = 0;           // k_ext key sets created (F8, AES-256, Twofish, Skein): k_ext runs only when > 0
     uint32_t n_skein = 0;         // Skein-MAC key sets created: k_skein runs only when > 0
+    GcmKeys *d_gcmkeys = nullptr; // 1 per key set, allocated with the first AES-GCM factory
+    uint32_t n_gcm = 0;           // AES-GCM key sets created: k_gcm and the walk's GCM instances only when > 0
+    bool aead = false;            // srtp_engine_enable_aead: new factories may carry the GCM policy
     uint32_t n_not_wide = 0;      // key sets the split path cannot run (not AES-CM / NULL cipher + HMAC-SHA1)
     uint32_t n_keysets = 0, max_keysets = 0;
     FactoryRec *d_factories = nullptr;
@@ -147,8 +151,18 @@ void dfree(void *p) {
 bool is_twofish(int enc) { return enc == SRTP_TWOFISH_ENCRYPTION || enc == SRTP_TWOFISHF8_ENCRYPTION; }
 bool is_f8(int enc) { return enc == SRTP_AESF8_ENCRYPTION || enc == SRTP_TWOFISHF8_ENCRYPTION; }
 
-bool policy_ok(const srtp_policy *p, bool rtcp) {
+// The one AES-GCM shape (RFC 7714; include/srtp_mi355x.h at SRTP_AESGCM_ENCRYPTION)
+bool is_gcm_policy(const srtp_policy *p) {
+    return p->enc_type == SRTP_AESGCM_ENCRYPTION && (p->enc_key_len == 16 || p->enc_key_len == 32) &&
+           p->auth_type == SRTP_NULL_AUTHENTICATION && p->auth_key_len == 0 && p->auth_tag_len == 16 &&
+           p->salt_key_len == 12;
+}
+
+// aead: the engine's switch (srtp_engine_enable_aead); off, a GCM-typed policy
+// is refused like any unknown cipher
+bool policy_ok(const srtp_policy *p, bool rtcp, bool aead = false) {
     if (!p) return false;
+    if (p->enc_type == SRTP_AESGCM_ENCRYPTION) return aead && is_gcm_policy(p);
     if (p->enc_type != SRTP_NULL_ENCRYPTION && p->enc_type != SRTP_AESCM_ENCRYPTION &&
         p->enc_type != SRTP_AESF8_ENCRYPTION && !is_twofish(p->enc_type))
         return false;
@@ -181,6 +195,34 @@ bool policy_ok(const srtp_policy *p, bool rtcp) {
 // (the NULL cipher keeps the AES-128 PRF, see srtp_factory_create).
 int master_key_len(const srtp_policy *pol) {
     return pol->enc_type != SRTP_NULL_ENCRYPTION && pol->enc_key_len == 32 ? 32 : 16;
+}
+
+// A GCM key set (RFC 7714 11): the KeySet is stored as NULL cipher / NULL
+// authentication / tag length 0 with the mark in `pad` and `ext` clear, so the
+// kernels that do not know the mark take their NULL / NULL path on its
+// packets; the keys proper go to the GcmKeys table (k_gcm, the walk's re-check).
+void build_keyset_gcm(const uint8_t *mk, const uint8_t *ms, bool rtcp, const srtp_policy *pol, KeySet *ks,
+                      GcmKeys *gk) {
+    memset(ks, 0, sizeof *ks);
+    memset(gk, 0, sizeof *gk);
+    uint8_t enc[32], salt[14];
+    derive_session_keys_gcm(mk, pol->enc_key_len, ms, rtcp, enc, salt);
+    GcmKeyArg ka;
+    gcm_key_arg(enc, pol->enc_key_len, &ka);
+    memcpy(gk->rk, ka.rk, sizeof gk->rk);
+    gk->nr = ka.nr;
+    memcpy(gk->htab, ka.htab, sizeof gk->htab);
+    for (int i = 0; i < 3; i++)
+        gk->salt[i] = (uint32_t)salt[4 * i] | ((uint32_t)salt[4 * i + 1] << 8) |
+                      ((uint32_t)salt[4 * i + 2] << 16) | ((uint32_t)salt[4 * i + 3] << 24);
+    ks->enc_type = SRTP_NULL_ENCRYPTION;
+    ks->auth_type = SRTP_NULL_AUTHENTICATION;
+    ks->tag_len = 0;
+    ks->kind = rtcp ? SRTP_KIND_RTCP : SRTP_KIND_RTP;
+    ks->pad = kGcmMark;
+    memset(&ka, 0, sizeof ka);
+    memset(enc, 0, sizeof enc);
+    memset(salt, 0, sizeof salt);
 }
 
 void build_keyset(const uint8_t *mk, const uint8_t ms[14], bool rtcp, const srtp_policy *pol,
@@ -538,13 +580,15 @@ void srtp_engine_destroy(srtp_engine *e) {
         (void)hipMemset(e->d_tfkeys, 0, 2 * (size_t)e->max_keysets * sizeof(TwofishKeys));
     if (e->d_skkeys)
         (void)hipMemset(e->d_skkeys, 0, (size_t)e->max_keysets * sizeof(SkeinKeys));
+    if (e->d_gcmkeys)
+        (void)hipMemset(e->d_gcmkeys, 0, (size_t)e->max_keysets * sizeof(GcmKeys));
     free_scratch(e);
     for (auto &m : e->marks) {
         (void)hipEventDestroy(m.a);
         (void)hipEventDestroy(m.b);
     }
     for (auto ev : e->event_pool) (void)hipEventDestroy(ev);
-    void *ptrs[] = {e->d_keysets, e->d_extkeys, e->d_tfkeys, e->d_skkeys, e->d_factories, e->d_transformers, e->d_ctx_keys, e->d_ctx,
+    void *ptrs[] = {e->d_keysets, e->d_extkeys, e->d_tfkeys, e->d_skkeys, e->d_gcmkeys, e->d_factories, e->d_transformers, e->d_ctx_keys, e->d_ctx,
                     e->d_far, e->e_min, e->ctl, e->d_count, e->d_counters, e->h_seg, e->h_off, e->h_len,
                     e->h_cap, e->h_flags, e->h_status, e->h_tids};
     for (void *p : ptrs) dfree(p);
@@ -564,18 +608,43 @@ int srtp_factory_create(srtp_engine *e, int32_t sender, const uint8_t *mk, int32
     GUARD(e);
     // NULL-cipher profiles keep a 16-B master key + 14-B salt for the RFC 3711
     // 4.3 PRF (the reference throws there: SURVEY Q15) -- parity unpinned.
-    if (!policy_ok(srtp_pol, false) || !policy_ok(srtcp_pol, true))
+    if (!policy_ok(srtp_pol, false, e->aead) || !policy_ok(srtcp_pol, true, e->aead))
         return fail(e, SRTP_EPOLICY, "unsupported SRTP policy");
-    if (key_len < std::max(master_key_len(srtp_pol), master_key_len(srtcp_pol)) || salt_len < 14)
-        return fail(e, SRTP_EPOLICY, "master key / salt shorter than the policy");
+    const srtp_policy *pols[2] = {srtp_pol, srtcp_pol};
+    const bool gcm[2] = {srtp_pol->enc_type == SRTP_AESGCM_ENCRYPTION, srtcp_pol->enc_type == SRTP_AESGCM_ENCRYPTION};
+    // a GCM policy needs its own key and 12 salt bytes, any other its key and 14
+    for (int i = 0; i < 2; i++)
+        if (key_len < (gcm[i] ? pols[i]->enc_key_len : master_key_len(pols[i])) || salt_len < (gcm[i] ? 12 : 14))
+            return fail(e, SRTP_EPOLICY, "master key / salt shorter than the policy");
     if (e->factories.size() >= e->opts.max_factories || e->n_keysets + 2 > e->max_keysets)
         return fail(e, SRTP_EFULL, "factory table full");
     KeySet ks[2];
     ExtKeys f8[2];
     std::vector<TwofishKeys> tf(4);
     SkeinKeys sk[2];
-    build_keyset(mk, ms, false, srtp_pol, &ks[0], &f8[0], &tf[0], &sk[0]);
-    build_keyset(mk, ms, true, srtcp_pol, &ks[1], &f8[1], &tf[2], &sk[1]);
+    GcmKeys gk[2];
+    memset(gk, 0, sizeof gk);
+    for (int i = 0; i < 2; i++) {
+        if (gcm[i]) {
+            memset(&f8[i], 0, sizeof f8[i]);
+            std::fill(tf.begin() + 2 * i, tf.begin() + 2 * i + 2, TwofishKeys{});
+            memset(&sk[i], 0, sizeof sk[i]);
+            build_keyset_gcm(mk, ms, i == 1, pols[i], &ks[i], &gk[i]);
+        } else {
+            build_keyset(mk, ms, i == 1, pols[i], &ks[i], &f8[i], &tf[2 * i], &sk[i]);
+        }
+    }
+    if (gcm[0] || gcm[1]) {
+        if (!e->d_gcmkeys && dalloc(&e->d_gcmkeys, (size_t)e->max_keysets) != hipSuccess) {
+            memset(gk, 0, sizeof gk);
+            return fail(e, SRTP_ENOMEM, "AES-GCM key table");
+        }
+        // an enqueued bundle may hold the table pointer it was given: null before
+        // the first GCM factory, and then it runs no GCM pass
+        HIPCHK(e, hipMemcpy(e->d_gcmkeys + e->n_keysets, gk, sizeof gk, hipMemcpyHostToDevice));
+        e->n_gcm += (uint32_t)gcm[0] + (uint32_t)gcm[1];
+    }
+    memset(gk, 0, sizeof gk);
     const bool any_skein = srtp_pol->auth_type == SRTP_SKEIN_AUTHENTICATION ||
                            srtcp_pol->auth_type == SRTP_SKEIN_AUTHENTICATION;
     if (any_skein) {
@@ -601,7 +670,7 @@ int srtp_factory_create(srtp_engine *e, int32_t sender, const uint8_t *mk, int32
     HIPCHK(e, hipMemcpy(e->d_extkeys + e->n_keysets, f8, sizeof f8, hipMemcpyHostToDevice));
     e->n_ext += (uint32_t)(ks[0].ext + ks[1].ext);
     for (const KeySet &k : ks)
-        e->n_not_wide += (k.ext || k.auth_type != SRTP_HMACSHA1_AUTHENTICATION ||
+        e->n_not_wide += (k.ext || k.pad == kGcmMark || k.auth_type != SRTP_HMACSHA1_AUTHENTICATION ||
                           (k.enc_type != SRTP_AESCM_ENCRYPTION && k.enc_type != SRTP_NULL_ENCRYPTION))
                              ? 1u : 0u;
     memset(ks, 0, sizeof ks);
@@ -736,6 +805,8 @@ static int transform_locked(srtp_engine *e, int32_t reverse, const int32_t *tids
     a.tfkeys = e->d_tfkeys;
     a.skkeys = e->d_skkeys;
     a.has_skein = e->n_skein ? 1 : 0;
+    a.gcmkeys = e->d_gcmkeys;
+    a.has_gcm = e->n_gcm ? 1 : 0;
     a.factories = e->d_factories;
     a.transformers = e->d_transformers;
     a.ctx_keys = e->d_ctx_keys;
@@ -842,6 +913,7 @@ static int transform_locked(srtp_engine *e, int32_t reverse, const int32_t *tids
         HIPCHK(e, launch_unprotect(a, s));
         if (a.small_ctr) HIPCHK(e, launch_ctr_small(a, s)); // the speculative decryption
         if (e->n_skein) HIPCHK(e, launch_skein(a, s));
+        if (e->n_gcm) HIPCHK(e, launch_gcm(a, 1, s)); // tag check under the ROC guess
     }
     {
         StageTimer t(e, s, SRTP_STAGE_WALK);
@@ -864,12 +936,14 @@ static int transform_locked(srtp_engine *e, int32_t reverse, const int32_t *tids
         StageTimer t(e, s, SRTP_STAGE_DECRYPT);
         HIPCHK(e, launch_unprotect_fix(a, s));
         if (e->n_ext) HIPCHK(e, launch_ext(a, s));
+        if (e->n_gcm) HIPCHK(e, launch_gcm(a, 2, s)); // the accepted packets deciphered
     } else {
         StageTimer t(e, s, SRTP_STAGE_PROTECT);
         if (a.small_ctr) HIPCHK(e, launch_ctr_small(a, s)); // the keystream, then k_protect MACs
         HIPCHK(e, launch_protect(a, s));
         if (e->n_ext) HIPCHK(e, launch_ext(a, s));
         if (e->n_skein) HIPCHK(e, launch_skein(a, s));
+        if (e->n_gcm) HIPCHK(e, launch_gcm(a, 0, s)); // sealed: tag, SRTCP's E|index word
     }
     }
     HIPCHK(e, hipEventRecord(dev_event ? e->ev_dev : e->ev_last, s));
@@ -1297,6 +1371,34 @@ int srtp_aes_gcm_device(srtp_engine *e, int32_t open, const uint8_t *key, int32_
     const hipError_t err = launch_gcm_aead(g, (hipStream_t)stream);
     memset(&g.key, 0, sizeof g.key);
     if (err != hipSuccess) return fail(e, SRTP_EDEVICE, std::string("k_gcm_aead: ") + hipGetErrorString(err));
+    return SRTP_OK;
+}
+
+int srtp_engine_enable_aead(srtp_engine *e, int32_t on) {
+    if (!e) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    e->aead = on != 0; // existing GCM factories keep working either way
+    return SRTP_OK;
+}
+
+int srtp_gcm_packet_job(int32_t kind, int32_t reverse, int32_t len, int32_t cap, int32_t header_len,
+                        uint32_t flags, int32_t e_bit, srtp_gcm_job *out) {
+    if (!out || (kind != SRTP_KIND_RTP && kind != SRTP_KIND_RTCP)) return SRTP_EINVAL;
+    static_assert(SRTP_GCM_HDR_THROW == kGcmHdrThrow && SRTP_STATUS_DROP_AUTH == kGcmStDropAuth &&
+                      SRTP_STATUS_ERR_CAPACITY == kGcmStCapacity && SRTP_STATUS_ERR_MALFORMED == kGcmStMalformed &&
+                      SRTP_STATUS_DROP_INVALID == kGcmStInvalid && SRTP_STATUS_ERR_INTERNAL == kGcmStInternal &&
+                      (SRTP_PKT_FLAG_DISCARD | SRTP_PKT_FLAG_SILENCE) == kGcmFlagNoDecipher,
+                  "gcm_job.h restates these constants");
+    const GcmJob j = gcm_packet_job(kind, reverse ? 1 : 0, len, cap, header_len, flags, e_bit ? 1 : 0);
+    out->status = j.status;
+    out->new_len = j.new_len;
+    out->aad_len = j.aad_len;
+    out->word_at = j.word_at;
+    out->word_aad = j.word_aad;
+    out->data_at = j.data_at;
+    out->data_len = j.data_len;
+    out->tag_at = j.tag_at;
+    out->decipher = j.decipher;
     return SRTP_OK;
 }
 

@@ -97,6 +97,10 @@ struct BundleArgs {
     // applied by k_ctr_small (a lane per counter-block pair), the fused
     // kernels only MAC those packets; 2: the split path (k_ctr_wide + k_mac_wide)
     int32_t small_ctr;
+    // AES-GCM key sets (RFC 7714): [keysets] their keys (null: none yet); has_gcm
+    // selects the walk's GCM instances and the k_gcm passes
+    const GcmKeys *gcmkeys;
+    int32_t has_gcm;
 };
 
 // Layout of the sort's scratch (one allocation of sort_temp_bytes(n_max)).
@@ -130,6 +134,11 @@ hipError_t launch_unprotect(const BundleArgs &a, hipStream_t s);
 // k_unprotect's ROC guess (after k_unprotect, before the walk).  Protect: their
 // trailers (after k_ext).
 hipError_t launch_skein(const BundleArgs &a, hipStream_t s);
+// Engines with AES-GCM key sets (k_gcm).  mode 1 (unprotect, beside k_skein):
+// the tag check under k_unprotect's ROC guess; mode 2 (unprotect, after
+// k_unprotect_fix): the accepted packets deciphered; mode 0 (protect, after
+// k_protect): sealed, tag and SRTCP's E|index word written.
+hipError_t launch_gcm(const BundleArgs &a, int mode, hipStream_t s);
 hipError_t launch_walk(const BundleArgs &a, int limit_pass, hipStream_t s);
 hipError_t launch_protect(const BundleArgs &a, hipStream_t s);
 // BundleArgs::small_ctr: the keystream of the AES-CM + HMAC-SHA1 packets, one

@@ -22,6 +22,11 @@
 //   k_skein    [engines with Skein-MAC key sets] Skein-512 tag check / trailer.
 //   k_ext      [engines with F8 / AES-256 / Twofish / Skein key sets] their
 //              ciphers (and the F8 / AES-256 HMAC trailers).
+//   k_gcm      [engines with AES-GCM key sets, RFC 7714] a lane per packet around
+//              gcm_packet: the tag check before the walk, the decipher after
+//              k_unprotect_fix, the seal after k_protect; every packet offset from
+//              gcm_packet_job (gcm_job.h).  Such an engine's walk runs in the GCM
+//              instances of k_walk (walk_one_gcm for those contexts' records).
 //   k_protect  [protect] one lane per packet: fused AES-CM keystream + XOR +
 //              HMAC-SHA1 (one read and one write of the packet bytes).
 //   k_unprotect_fix [unprotect] statuses/lengths out; undoes/redoes the rare
@@ -46,6 +51,7 @@
 
 
 #include "../../include/srtp_mi355x.h"
+#include "gcm_job.h"
 #include "srtp_kernels.h"
 
 namespace srtp {
@@ -1992,6 +1998,180 @@ struct WalkCtx {
     bool check_replay, reverse;
 };
 
+// ------------------------------------------------- AES-GCM key sets (RFC 7714)
+// The 12 IV bytes as little-endian words: (0x0000 || SSRC || ROC || SEQ) ^ salt
+// (RFC 7714 8.1) and (0x0000 || SSRC || 0x0000 || 0|index) ^ salt (9.1).
+// ssrc_le: the SSRC's four bytes as they lie in the packet, as one LE word.
+__device__ __forceinline__ void gcm_iv_rtp(const uint32_t salt[3], uint32_t ssrc_le, uint32_t roc, uint32_t seq,
+                                           uint32_t iv[3]) {
+    const uint32_t r = bswap(roc), sq = ((seq >> 8) & 0xffu) | ((seq & 0xffu) << 8);
+    iv[0] = salt[0] ^ (ssrc_le << 16);
+    iv[1] = salt[1] ^ (ssrc_le >> 16) ^ (r << 16);
+    iv[2] = salt[2] ^ (r >> 16) ^ (sq << 16);
+}
+__device__ __forceinline__ void gcm_iv_rtcp(const uint32_t salt[3], uint32_t ssrc_le, uint32_t index,
+                                            uint32_t iv[3]) {
+    iv[0] = salt[0] ^ (ssrc_le << 16);
+    iv[1] = salt[1] ^ (ssrc_le >> 16);
+    iv[2] = salt[2] ^ bswap(index & 0x7FFFFFFFu);
+}
+
+// One AES block under a lane's own round keys by the plain T-table in global
+// memory (d_te0): the walk's one-block tag re-check needs no LDS image.
+__device__ __forceinline__ void aes_block_plain(const uint32_t *__restrict__ rk, int nr, uint32_t s[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) s[j] ^= rk[j];
+    for (int r = 1; r < nr; r++) {
+        uint32_t t[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            t[j] = d_te0[s[j] & 0xffu] ^ rotl(d_te0[(s[(j + 1) & 3] >> 8) & 0xffu], 8) ^
+                   rotl(d_te0[(s[(j + 2) & 3] >> 16) & 0xffu], 16) ^ rotl(d_te0[s[(j + 3) & 3] >> 24], 24) ^
+                   rk[4 * r + j];
+#pragma unroll
+        for (int j = 0; j < 4; j++) s[j] = t[j];
+    }
+    uint32_t t[4]; // SubBytes (the table's second byte) and ShiftRows
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+        t[j] = (((d_te0[s[j] & 0xffu] >> 8) & 0xffu) | (((d_te0[(s[(j + 1) & 3] >> 8) & 0xffu] >> 8) & 0xffu) << 8) |
+                (((d_te0[(s[(j + 2) & 3] >> 16) & 0xffu] >> 8) & 0xffu) << 16) |
+                (((d_te0[s[(j + 3) & 3] >> 24] >> 8) & 0xffu) << 24)) ^
+               rk[4 * nr + j];
+#pragma unroll
+    for (int j = 0; j < 4; j++) s[j] = t[j];
+}
+
+// The walk's re-check of a GCM SRTP tag under ROC g: k_gcm's verify pass left
+// S = GHASH ^ received tag in mid[5p .. 5p + 3] (GHASH does not depend on the
+// IV), so the tag matches under g iff E_K(IV(g) || 1) == S -- one block.
+__device__ __forceinline__ bool gcm_reverify(const BundleArgs &a, uint32_t ks_id, uint32_t slot, uint32_t p,
+                                             uint32_t seq, uint32_t g) {
+    const GcmKeys *gk = a.gcmkeys + ks_id;
+    const uint32_t ssrc_le = bswap((uint32_t)a.ctx_keys[slot]); // key = tid << 32 | SSRC
+    uint32_t iv[3], s[4];
+    gcm_iv_rtp(gk->salt, ssrc_le, g, seq, iv);
+    s[0] = iv[0]; s[1] = iv[1]; s[2] = iv[2]; s[3] = 0x01000000u;
+    aes_block_plain(gk->rk, gk->nr, s);
+    const uint32_t *S = a.mid + 5 * (size_t)p;
+    return ((s[0] ^ S[0]) | (s[1] ^ S[1]) | (s[2] ^ S[2]) | (s[3] ^ S[3])) == 0u;
+}
+
+// walk_one for a record of a GCM context (tests/gcm_ref.py process_one; every
+// length and offset from gcm_packet_job).  The rules differ from an HMAC
+// profile's in order: ERR_CAPACITY before any state; SRTP: the replay check,
+// then the header-length throw, then a packet too short for its tag
+// (DROP_AUTH), then the tag; SRTCP unprotect: too short for tag + index word
+// throws, too short for a header before them is DROP_AUTH, then replay, tag.
+__device__ __forceinline__ bool walk_one_gcm(const BundleArgs &a, uint32_t ks_id, uint32_t slot, const WalkCtx &c,
+                                             CtxState &st, const WalkRec &rec, uint32_t g0, uint32_t auth_ok,
+                                             bool dry, int32_t tid) {
+    const uint32_t p = rec.p & kRecIdxMask;
+    const int L = (int)(rec.lc & 0xffffu), C = (int)(rec.lc >> 16);
+    bool threw = false;
+    if (c.kind == SRTP_KIND_RTP) {
+        const uint32_t fl = (rec.p & kRecSkipDec) ? SRTP_PKT_FLAG_DISCARD : 0u;
+        const GcmJob j = gcm_packet_job(0, c.reverse ? 1 : 0, L, C, rec.h, fl, 1);
+        if (j.status == kGcmStCapacity || j.status == kGcmStInvalid || j.status == kGcmStInternal) {
+            a.w_status[p] = j.status;
+            return true;
+        }
+        const int seq = (int)rec.word;
+        if (!(st.flags & 1u)) { st.flags |= 1u; st.b = seq; }
+        int32_t g; // guessIndex, as walk_one
+        if (st.b < 32768) g = (seq - st.b > 32768) ? (int32_t)((uint32_t)st.a - 1u) : st.a;
+        else g = (st.b - 32768 > seq) ? (int32_t)((uint32_t)st.a + 1u) : st.a;
+        st.g = g;
+        const int64_t gi = java_lshl((int64_t)g, 16) | seq;
+        const int64_t local = java_lshl((int64_t)st.a, 16) | st.b;
+        const int64_t delta = gi - local;
+        if (c.check_replay && delta <= 0) {
+            if (-delta > 64 || (((uint64_t)st.window >> ((-delta) & 63)) & 1u)) {
+                a.w_status[p] = SRTP_STATUS_DROP_REPLAY;
+                return true;
+            }
+        }
+        if (j.status == kGcmStMalformed) {
+            threw = true;
+        } else if (j.status != kGcmNoStatus) { // DROP_AUTH: too short for its tag
+            a.w_len[p] = (uint32_t)j.new_len;
+            a.w_status[p] = j.status;
+            return true;
+        } else {
+            if (c.reverse) {
+                bool ok;
+                if ((uint32_t)g == g0) {
+                    ok = (auth_ok & 1u) != 0;
+                } else {
+                    ok = gcm_reverify(a, ks_id, slot, p, (uint32_t)seq, (uint32_t)g);
+                    atomicAdd(&a.counters[kCtrRocRecheck], 1ull);
+                }
+                if (!ok) {
+                    a.w_len[p] = (uint32_t)j.new_len;
+                    a.w_status[p] = SRTP_STATUS_DROP_AUTH;
+                    return true;
+                }
+            }
+            a.w_cw[p] = (uint32_t)g;
+            a.w_len[p] = (uint32_t)j.new_len;
+            if (delta > 0) st.window = (uint64_t)java_lshl((int64_t)st.window, delta) | 1ull;
+            else st.window |= (uint64_t)(int64_t)java_ishl1((int32_t)(-delta));
+            if (g == st.a) {
+                if (seq > st.b) st.b = seq & 0xffff;
+            } else if (g == (int32_t)((uint32_t)st.a + 1u)) {
+                st.b = seq & 0xffff;
+                st.a = g;
+            }
+        }
+    } else if (!c.reverse) {
+        const GcmJob j = gcm_packet_job(1, 0, L, C, 0, 0u, 1);
+        if (j.status != kGcmNoStatus) { // ERR_CAPACITY
+            a.w_status[p] = j.status;
+            return true;
+        }
+        a.w_cw[p] = (uint32_t)st.a;
+        a.w_len[p] = (uint32_t)j.new_len;
+        st.a = (int32_t)(((uint32_t)st.a + 1u) & 0x7FFFFFFFu);
+    } else {
+        const GcmJob j = gcm_packet_job(1, 1, L, C, 0, 0u, 1);
+        if (j.status == kGcmStMalformed) {
+            threw = true;
+        } else if (j.status != kGcmNoStatus) { // DROP_AUTH: no room for a header before tag + word
+            a.w_len[p] = (uint32_t)j.new_len;
+            a.w_status[p] = j.status;
+            return true;
+        } else {
+            // k_parse read the word at L - 4 - (tag length of the key set it saw);
+            // a GCM key set is stored with tag length 0, and j.word_at is L - 4
+            uint32_t word = rec.word;
+            if (rec.h != 0) word = ld_be32(a.seg + a.off[p] + j.word_at);
+            const int32_t index = (int32_t)(word & 0x7FFFFFFFu);
+            const int64_t delta = (int64_t)(int32_t)((uint32_t)index - (uint32_t)st.b);
+            if (delta <= 0 && (-delta > 64 || (((uint64_t)st.window >> ((-delta) & 63)) & 1u))) {
+                a.w_status[p] = SRTP_STATUS_DROP_REPLAY;
+                return true;
+            }
+            a.w_len[p] = (uint32_t)j.new_len;
+            if (!(auth_ok & 1u)) { a.w_status[p] = SRTP_STATUS_DROP_AUTH; return true; }
+            a.w_cw[p] = word;
+            const int32_t d2 = (int32_t)((uint32_t)st.b - (uint32_t)index);
+            if (d2 > 0) st.window = (uint64_t)java_lshl((int64_t)st.window, d2) | 1ull;
+            else st.window |= (uint64_t)(int64_t)java_ishl1(d2);
+            st.b = index;
+        }
+    }
+    if (threw) {
+        a.w_status[p] = SRTP_STATUS_ERR_MALFORMED;
+        if (a.abort_on_error) {
+            if (dry) atomicMin(&a.e_min[tid], (int32_t)p);
+            return false;
+        }
+        return true;
+    }
+    a.w_status[p] = SRTP_STATUS_OK;
+    return true;
+}
+
 // Processes one packet; returns false when the rest of the context's packets
 // are aborted (a throw with abort_on_error).
 template <bool SK>
@@ -2857,8 +3037,20 @@ struct WalkShared {
 static_assert(kLongStep <= kWalkWin, "walk_long stages a step in the first pass's arrays");
 static_assert(kLongStep <= kWalkSpan, "a medium chain's walk_long step keeps its ROCs in s_pkey");
 
+// The context in slot `key` (a walked record's key) has a GCM key set; false
+// at compile time in the instances of engines without one.
+template <bool GCM>
+__device__ __forceinline__ bool gcm_slot(const BundleArgs &a, uint32_t key) {
+    if constexpr (GCM) return key <= a.ctx_mask && a.keysets[a.ctx[key].ks].pad == kGcmMark;
+    else return false;
+}
+
 // Tile `blk` of `nblk` (k_walk: blockIdx.x of gridDim.x), by one wave.
-template <bool REV, bool SK, int PASS>
+// GCM: the engine holds AES-GCM key sets.  Every record of a GCM context's
+// chain goes through walk_one_gcm, one lane per chain as SRTCP chains go:
+// the fast prefix, the medium chains and the chain pass (walk_long's and
+// chain_part's speculation) leave such chains alone.
+template <bool REV, bool SK, int PASS, bool GCM = false>
 __device__ __forceinline__ void walk_tile(const BundleArgs &a, WalkShared<REV> &sh, uint32_t blk, uint32_t nblk) {
     constexpr int limit_pass = PASS;
     WalkRec *const s_rec = sh.rec;
@@ -2937,7 +3129,9 @@ __device__ __forceinline__ void walk_tile(const BundleArgs &a, WalkShared<REV> &
     if constexpr (PASS == 1) if (chain_pass) {
         const uint32_t epoch = a.serial + 1u;
         // the part at the tile start that continues a chain from the tile before
-        const uint32_t key0 = s_key[0];
+        uint32_t key0 = s_key[0];
+        if constexpr (GCM)
+            if (gcm_slot<true>(a, key0)) key0 = kNoSlot; // past ctx_mask: a GCM chain is never the chain pass's
         bool in_long = false;
         if (base && key0 == prev_key && key0 <= a.ctx_mask) {
             if (s_pkey[0] == key0) {
@@ -2954,7 +3148,9 @@ __device__ __forceinline__ void walk_tile(const BundleArgs &a, WalkShared<REV> &
             }
         }
         // the run holding the tile's last record, and where it starts in the tile
-        const uint32_t keyl = s_key[span - 1];
+        uint32_t keyl = s_key[span - 1];
+        if constexpr (GCM)
+            if (gcm_slot<true>(a, keyl)) keyl = kNoSlot;
         uint32_t runs = span; // first position of keyl's run in the tile
 #pragma unroll
         for (int k = 0; k < kWalkPer; k++) {
@@ -3047,6 +3243,49 @@ __device__ __forceinline__ void walk_tile(const BundleArgs &a, WalkShared<REV> &
         const uint32_t j = s_start[q];
         const uint32_t key = s_key[j];
         const uint32_t slot = key;
+        if constexpr (GCM) {
+            // A GCM context's chain, whatever its length: every record through
+            // walk_one_gcm, from the staged window and then from global memory
+            // (the serial walk below, without its fast prefix).
+            if (gcm_slot<true>(a, key)) {
+                CtxState st = a.ctx[slot];
+                const uint32_t ks_id = st.ks;
+                const KeySet *ks = a.keysets + ks_id;
+                WalkCtx c;
+                c.enc = ks->enc_type; c.auth = ks->auth_type; c.T = ks->tag_len; c.kind = ks->kind;
+                c.check_replay = a.check_replay != 0;
+                c.reverse = REV;
+                const int32_t tid = (int32_t)(a.ctx_keys[slot] >> 32);
+                const int32_t E = limit_pass ? a.e_min[tid] : 0x7fffffff;
+                const uint32_t first_p = s_rec[j].p & kRecIdxMask;
+                bool more = true;
+                uint32_t jj = j;
+                for (; jj < win && more; jj++) {
+                    if (s_key[jj] != key) { more = false; break; }
+                    const WalkRec r = s_rec[jj];
+                    if (limit_pass && (int32_t)(r.p & kRecIdxMask) > E) { more = false; break; }
+                    more = walk_one_gcm(a, ks_id, slot, c, st, r, REV ? s_g0[jj] : 0u, REV ? s_ok[jj] : 0u, dry, tid);
+                }
+                for (uint32_t i = base + jj; more && i < a.n; i++) {
+                    if (a.sk_out[i] != key) break;
+                    const WalkRec r = a.sv_out[i];
+                    if (limit_pass && (int32_t)(r.p & kRecIdxMask) > E) break;
+                    uint32_t g0 = 0u, ok = 0u;
+                    if (REV) {
+                        const uint2 go = gok_of(a, r.p & kRecIdxMask);
+                        g0 = go.x; ok = go.y;
+                    }
+                    more = walk_one_gcm(a, ks_id, slot, c, st, r, g0, ok, dry, tid);
+                }
+                if (dry) continue;
+                if (limit_pass && st.birth == a.serial && (int32_t)first_p > E) {
+                    __hip_atomic_store(&a.ctx_keys[slot], kTombKey, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    continue;
+                }
+                a.ctx[slot] = st;
+                continue;
+            }
+        }
         // long chains are the chain pass's, unless abort-on-throw needs the serial walk
         if (chains && long_from(j, key)) {
             atomicOr(&a.ctl->n_long, 1u);
@@ -3178,10 +3417,10 @@ __device__ __forceinline__ void walk_tile(const BundleArgs &a, WalkShared<REV> &
     }
 }
 
-template <bool REV, bool SK, int PASS>
+template <bool REV, bool SK, int PASS, bool GCM = false>
 __global__ __launch_bounds__(kWalkBlock) void k_walk(BundleArgs a) {
     __shared__ WalkShared<REV> sh;
-    walk_tile<REV, SK, PASS>(a, sh, blockIdx.x, gridDim.x);
+    walk_tile<REV, SK, PASS, GCM>(a, sh, blockIdx.x, gridDim.x);
 }
 
 // ====================================================== final status helper
@@ -4651,11 +4890,38 @@ __device__ __forceinline__ void gcm_absorb_bytes(const uint32_t *tab, uint64_t &
     }
 }
 
+// GHASH of the AAD: bytes [0, n) of p, then tail_len (0 or 4) bytes of `tail`
+// (a little-endian word) right behind them, zero-padded to whole blocks.  The
+// tail is spliced into the block(s) it falls in; no packet byte is copied.
+__device__ __forceinline__ void gcm_absorb_aad(const uint32_t *tab, uint64_t &zh, uint64_t &zl,
+                                               const uint8_t *p, int n, uint32_t tail, int tail_len) {
+    if (!tail_len) {
+        gcm_absorb_bytes(tab, zh, zl, p, n);
+        return;
+    }
+    const int full = n & ~15;
+    gcm_absorb_bytes(tab, zh, zl, p, full);
+    const int m = n - full; // 0..15 head bytes in the block the tail starts in
+    uint32_t w[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    if (m) gcm_load(p + full, m, w);
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const int o = 4 * k - m; // tail byte i sits at block position m + i
+        if (o > -4 && o < 4) w[k] |= o >= 0 ? (tail >> (8 * o)) : (tail << (8 * -o));
+    }
+    gcm_absorb(tab, zh, zl, w);
+    if (m + 4 > 16) gcm_absorb(tab, zh, zl, w + 4);
+}
+
 // One packet: AAD at aad[0, aad_len), the data right behind it, len bytes.
+// tail_len = 4: the AAD goes on with the four bytes of `tail` (SRTCP's E|index
+// word, which lies behind the tag, not behind the header); 0: no tail.
 struct GcmPkt {
     uint8_t *aad;
     int aad_len, len;
     uint32_t iv[3]; // the 12 IV bytes as little-endian words
+    uint32_t tail = 0u;
+    int tail_len = 0;
 };
 
 enum { kGcmSeal = 0, kGcmVerify = 1, kGcmDecipher = 2 };
@@ -4668,14 +4934,16 @@ enum { kGcmSeal = 0, kGcmVerify = 1, kGcmDecipher = 2 };
 // tag[]: the 16 tag bytes as little-endian words.  Cipher: encrypt2() of two
 // blocks, as k_ext's ciphers; the mask block E_K(IV || 1) shares the first
 // pair with counter 2.  Touches no byte outside [aad, aad + aad_len + len).
+// mask_out (verify mode, may be null): E_K(IV || 1), so that a caller can keep
+// GHASH ^ received tag for a re-check under another IV.
 template <int MODE, class Cipher>
 __device__ __forceinline__ void gcm_packet(const Cipher &cipher, const uint32_t *tab, const GcmPkt &j,
-                                           uint32_t tag[4]) {
+                                           uint32_t tag[4], uint32_t *mask_out = nullptr) {
     uint8_t *data = j.aad + j.aad_len;
     const int nb = (j.len + 15) >> 4;
     uint64_t zh = 0ull, zl = 0ull;
     uint32_t mask[4] = {0u, 0u, 0u, 0u};
-    if (MODE != kGcmDecipher) gcm_absorb_bytes(tab, zh, zl, j.aad, j.aad_len);
+    if (MODE != kGcmDecipher) gcm_absorb_aad(tab, zh, zl, j.aad, j.aad_len, j.tail, j.tail_len);
     if (MODE == kGcmVerify) gcm_absorb_bytes(tab, zh, zl, data, j.len);
     // counter blocks in pairs: c, c + 1; counter c ciphers data block c - 2
     for (int c = MODE == kGcmDecipher ? 2 : 1; c == 1 || c - 2 < nb; c += 2) {
@@ -4710,7 +4978,11 @@ __device__ __forceinline__ void gcm_packet(const Cipher &cipher, const uint32_t 
         }
     }
     if (MODE == kGcmDecipher) return;
-    gcm_mult_xor(tab, zh, zl, (uint64_t)j.aad_len * 8ull, (uint64_t)j.len * 8ull);
+    gcm_mult_xor(tab, zh, zl, (uint64_t)(j.aad_len + j.tail_len) * 8ull, (uint64_t)j.len * 8ull);
+    if (MODE == kGcmVerify && mask_out) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) mask_out[k] = mask[k];
+    }
     tag[0] = bswap((uint32_t)(zh >> 32)) ^ mask[0];
     tag[1] = bswap((uint32_t)zh) ^ mask[1];
     tag[2] = bswap((uint32_t)(zl >> 32)) ^ mask[2];
@@ -4784,6 +5056,138 @@ __global__ __launch_bounds__(kGcmBlock) void k_gcm_aead(GcmBatch g) {
     const bool ok = ((tag[0] ^ got[0]) | (tag[1] ^ got[1]) | (tag[2] ^ got[2]) | (tag[3] ^ got[3])) == 0u;
     g.result[i] = ok ? 0 : 1;
     if (ok) gcm_packet<kGcmDecipher>(cipher, tab, j, tag);
+}
+
+// ============================================================== k_gcm
+// The packets of an engine's AES-GCM key sets (RFC 7714), a lane per packet,
+// in three passes around gcm_packet (MODE):
+//   verify    unprotect, beside k_skein: after k_unprotect wrote the ROC guess
+//             g0, before the walk.  The tag check under g0 (SRTCP: under the
+//             index word) goes to gok[2p + 1]; S = GHASH ^ received tag to
+//             mid[5p .. 5p + 3] for the walk's one-block re-check.
+//   decipher  unprotect, after k_unprotect_fix: packets whose final status is
+//             OK, but no SRTP packet flagged DISCARD / SILENCE and no SRTCP
+//             packet with E = 0.
+//   seal      protect, after k_protect: final-status-OK packets; writes the
+//             tag and, for SRTCP, the E|index word behind it.
+// Whether a lane has a packet to do is decided from the packet index, the
+// final status (the two post-walk modes), p_slot and the key set's mark alone;
+// no packet pointer or table index is formed before.  Every offset into the
+// packet then comes from gcm_packet_job, which hands out only ranges inside
+// [0, cap).  One pass per key set among a wave's lanes, as for_each_keyset
+// runs them, with the wave staging that key set's GHASH table in its own 256
+// LDS bytes behind the T-table image first (which needs all its lanes, so the
+// loop is written out here); the round keys are wave-uniform.
+template <int MODE>
+__device__ __forceinline__ void gcm_one(const BundleArgs &a, const char *__restrict__ lds, const TeBase &tb,
+                                        const uint32_t *tab, uint32_t ks_u, uint32_t p) {
+    const KeySet *ks = a.keysets + ks_u;
+    const GcmKeys *gk = a.gcmkeys + ks_u;
+    const bool rtp = sgpr((uint32_t)ks->kind) == (uint32_t)SRTP_KIND_RTP;
+    const int trailer = rtp ? kGcmTag : kGcmTag + 4;
+    const uint32_t cap_u = a.cap[p], len_u = a.len[p];
+    if (cap_u > 65535u || len_u > 65535u) return; // k_parse refused such a packet
+    const int C = (int)cap_u;
+    // the length the packet came with: a.len still holds it before the walk;
+    // after the final statuses it holds the new one (status OK here)
+    const int L = MODE == kGcmVerify ? (int)len_u : MODE == kGcmSeal ? (int)len_u - trailer : (int)len_u + trailer;
+    if (MODE == kGcmVerify) a.gok[2 * (size_t)p + 1] = 0u;
+    if (L < 12 || L > C) return; // the job would say so too; no header byte is read before this
+    uint8_t *pkt = a.seg + a.off[p];
+    const uint32_t fl = a.flags ? a.flags[p] : 0u;
+    const uint32_t salt[3] = {sgpr(gk->salt[0]), sgpr(gk->salt[1]), sgpr(gk->salt[2])};
+    GcmJob j;
+    GcmPkt gp;
+    gp.aad = pkt;
+    if (rtp) {
+        const uint32_t w0 = *reinterpret_cast<const uint32_t *>(pkt);     // V/P/X/CC, M/PT, SEQ
+        const uint32_t w2 = *reinterpret_cast<const uint32_t *>(pkt + 8); // SSRC
+        const int32_t h = rtp_header_len(pkt, w0 & 0xffu, C);
+        j = gcm_packet_job(0, MODE == kGcmSeal ? 0 : 1, L, C, h, fl, 1);
+        if (j.status != kGcmNoStatus) return;
+        const uint32_t roc = MODE == kGcmVerify ? a.gok[2 * (size_t)p] : a.w_cw[p];
+        gcm_iv_rtp(salt, w2, roc, bswap(w0) & 0xffffu, gp.iv);
+    } else {
+        const uint32_t w1 = *reinterpret_cast<const uint32_t *>(pkt + 4); // SSRC
+        uint32_t word;
+        if (MODE == kGcmSeal) {
+            j = gcm_packet_job(1, 0, L, C, 0, 0u, 1);
+            if (j.status != kGcmNoStatus) return;
+            word = (a.w_cw[p] & 0x7FFFFFFFu) | 0x80000000u; // always E = 1 (RFC 7714 9.1)
+        } else {
+            j = gcm_packet_job(1, 1, L, C, 0, 0u, 1); // where the word lies does not depend on E
+            if (j.status != kGcmNoStatus) return;
+            word = ld_be32(pkt + j.word_at);
+            j = gcm_packet_job(1, 1, L, C, 0, 0u, (int)(word >> 31));
+            if (j.status != kGcmNoStatus) return;
+            if (MODE == kGcmDecipher && !(word >> 31)) return; // E = 0: nothing was ciphered
+        }
+        gcm_iv_rtcp(salt, w1, word, gp.iv);
+        gp.tail = bswap(word);
+        gp.tail_len = 4;
+    }
+    if (MODE == kGcmDecipher && !j.decipher) return; // DISCARD / SILENCE
+    gp.aad_len = j.aad_len;
+    gp.len = j.data_len;
+    RoundKeys256 rk;
+    load_rk256_uniform(gk->rk, rk);
+    const GcmBatchCipher cipher{lds, tb, rk, sgpr((uint32_t)gk->nr) == 14u};
+    uint32_t tag[4];
+    if (MODE == kGcmDecipher) {
+        gcm_packet<kGcmDecipher>(cipher, tab, gp, tag);
+    } else if (MODE == kGcmSeal) {
+        gcm_packet<kGcmSeal>(cipher, tab, gp, tag);
+        gcm_store(pkt + j.tag_at, 16, tag);
+        if (j.word_at >= 0) {
+            const uint32_t w[4] = {gp.tail, 0u, 0u, 0u};
+            gcm_store(pkt + j.word_at, 4, w);
+        }
+    } else {
+        uint32_t mask[4], got[4];
+        gcm_packet<kGcmVerify>(cipher, tab, gp, tag, mask);
+        gcm_load(pkt + j.tag_at, 16, got);
+        uint32_t *S = a.mid + 5 * (size_t)p;
+        uint32_t diff = 0u;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            diff |= tag[k] ^ got[k];
+            S[k] = tag[k] ^ mask[k] ^ got[k];
+        }
+        a.gok[2 * (size_t)p + 1] = diff == 0u ? 1u : 0u;
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kGcmBlock) void k_gcm(BundleArgs a) {
+    __shared__ uint32_t s_te[kTeWords + (kGcmBlock / 64) * kGcmTabWords]; // the image stays at LDS 0
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    bool todo = false;
+    uint32_t ks_id = 0u;
+    if (p < a.n && (MODE == kGcmVerify || a.status[p] == SRTP_STATUS_OK)) {
+        const uint32_t slot = a.p_slot[p];
+        if (slot != kNoSlot) {
+            ks_id = a.ctx[slot].ks;
+            todo = a.keysets[ks_id].pad == kGcmMark;
+        }
+    }
+    if (!__syncthreads_or(todo)) return;
+    fill_te4(s_te);
+    const TeBase tb = te_base();
+    const char *lds = reinterpret_cast<const char *>(s_te);
+    uint32_t *tab = s_te + kTeWords + (threadIdx.x >> 6) * kGcmTabWords;
+    const uint32_t lane = threadIdx.x & 63u;
+    while (true) { // for_each_keyset, with the table staged by the whole wave
+        const unsigned long long m = __ballot(todo);
+        if (m == 0ull) break;
+        const uint32_t ks_u = (uint32_t)__builtin_amdgcn_readlane((int)ks_id, __ffsll((long long)m) - 1);
+        tab[lane] = reinterpret_cast<const uint32_t *>(a.gcmkeys[ks_u].htab)[lane];
+        walk_sync(); // the wave's own LDS writes, before its lanes read the table
+        if (todo && ks_id == ks_u) {
+            gcm_one<MODE>(a, lds, tb, tab, ks_u, p);
+            todo = false;
+        }
+        walk_sync(); // the table is rewritten by the next pass
+    }
 }
 
 // ============================================================== maintenance
@@ -4933,11 +5337,24 @@ hipError_t launch_gcm_aead(const GcmBatch &g, hipStream_t s) {
     hipLaunchKernelGGL(k_gcm_aead, dim3((g.n + b - 1) / b), dim3(b), 0, s, g);
     return hipGetLastError();
 }
+hipError_t launch_gcm(const BundleArgs &a, int mode, hipStream_t s) {
+    const uint32_t b = aes_block(a.n, (uint32_t)kGcmBlock);
+    const dim3 grid((a.n + b - 1) / b), block(b);
+    if (mode == kGcmVerify) hipLaunchKernelGGL(k_gcm<kGcmVerify>, grid, block, 0, s, a);
+    else if (mode == kGcmDecipher) hipLaunchKernelGGL(k_gcm<kGcmDecipher>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(k_gcm<kGcmSeal>, grid, block, 0, s, a);
+    return hipGetLastError();
+}
 
 hipError_t launch_walk(const BundleArgs &a, int limit_pass, hipStream_t s) {
     const uint32_t spans = (a.n + kWalkSpan - 1) / kWalkSpan;
     const dim3 grid(spans);
-    if (a.reverse && a.has_skein) {
+    if (a.has_gcm) { // engines with AES-GCM key sets: instances of their own (with the Skein re-check)
+        if (a.reverse && limit_pass) hipLaunchKernelGGL((k_walk<true, true, 1, true>), grid, dim3(kWalkBlock), 0, s, a);
+        else if (a.reverse) hipLaunchKernelGGL((k_walk<true, true, 0, true>), grid, dim3(kWalkBlock), 0, s, a);
+        else if (limit_pass) hipLaunchKernelGGL((k_walk<false, false, 1, true>), grid, dim3(kWalkBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_walk<false, false, 0, true>), grid, dim3(kWalkBlock), 0, s, a);
+    } else if (a.reverse && a.has_skein) {
         if (limit_pass) hipLaunchKernelGGL((k_walk<true, true, 1>), grid, dim3(kWalkBlock), 0, s, a);
         else hipLaunchKernelGGL((k_walk<true, true, 0>), grid, dim3(kWalkBlock), 0, s, a);
     } else if (a.reverse) {

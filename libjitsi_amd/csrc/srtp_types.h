@@ -74,6 +74,22 @@ struct GcmKeyArg {
 };
 static_assert(sizeof(GcmKeyArg) == 512, "GcmKeyArg is 512 B");
 
+// AES-GCM key of a key set (SRTP_AESGCM_ENCRYPTION, RFC 7714), indexed by
+// key-set id in a table allocated with the first GCM factory.  The KeySet of
+// such a key set is stored as NULL cipher / NULL authentication / tag length 0
+// with kGcmMark in KeySet::pad, so every kernel that does not read the mark
+// takes its NULL / NULL path on its packets (no byte ciphered or MACed, no
+// trailer); k_gcm and the walk's GCM instances read the mark and this table.
+// GcmKeyArg's layout, with the 12-byte session salt in its padding words.
+struct alignas(256) GcmKeys {
+    uint32_t rk[60];      // 4 * (nr + 1) round-key words, little-endian column words; the rest 0
+    int32_t nr;           // 10 or 14
+    uint32_t salt[3];     // the session salt's 12 bytes as little-endian words
+    uint64_t htab[16][2]; // gcm_htable(E_K(0^128))
+};
+static_assert(sizeof(GcmKeys) == 512 && sizeof(GcmKeys) == sizeof(GcmKeyArg), "GcmKeys is 512 B");
+constexpr uint32_t kGcmMark = 0x47434d31u; // KeySet::pad of a GCM key set ("GCM1")
+
 struct FactoryRec {      // SRTPContextFactory
     int32_t open;        // 0 after close(): getDefaultContext() == null
     int32_t ks_rtp;      // key set of its default SRTPCryptoContext

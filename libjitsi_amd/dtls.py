@@ -27,6 +27,9 @@ PROFILES = (SRTP_AES128_CM_HMAC_SHA1_80, SRTP_AES128_CM_HMAC_SHA1_32, SRTP_NULL_
             SRTP_NULL_HMAC_SHA1_32)
 # TLS PRF of the negotiated version: DTLS 1.0 (the reference's offer,
 # TlsClientImpl.java:148-155) or DTLS 1.2
+# RFC 7714 14.2: AEAD_AES_128_GCM / AEAD_AES_256_GCM, answered only with aead=True
+# (the engine runs them behind SRTPEngine.enable_aead)
+AEAD_PROFILES = (N.PROFILE_AEAD_AES_128_GCM, N.PROFILE_AEAD_AES_256_GCM)
 PRF_TLS10, PRF_SHA256 = 0, 1
 EXPORTER_LABEL = b"EXTRACTOR-dtls_srtp"  # ExporterLabel.dtls_srtp
 
@@ -45,12 +48,18 @@ def export_keying_material(master_secret: bytes, client_random: bytes, server_ra
     return bytes(out)[:length]
 
 
-def profile_keys(profile: int, keying_material: Optional[bytes] = None) -> dict:
+def profile_keys(profile: int, keying_material: Optional[bytes] = None, aead: bool = False) -> dict:
     """Policies and split keys of a protection profile (:574-638).  Without
-    keying material: only the policies and keying_material_len."""
-    k = N.DtlsKeys()
+    keying material: only the policies and keying_material_len.  aead: also
+    answer AEAD_PROFILES (srtp_dtls_profile_keys_ex with SRTP_DTLS_AEAD)."""
     km = None if keying_material is None else bytes(keying_material)
-    rc = N.lib().srtp_dtls_profile_keys(profile, km, 0 if km is None else len(km), C.byref(k))
+    if aead:
+        k = N.DtlsKeysEx()
+        rc = N.lib().srtp_dtls_profile_keys_ex(profile, km, 0 if km is None else len(km), C.byref(k),
+                                               N.DTLS_AEAD)
+    else:
+        k = N.DtlsKeys()
+        rc = N.lib().srtp_dtls_profile_keys(profile, km, 0 if km is None else len(km), C.byref(k))
     if rc == -5:
         raise ValueError("srtpProtectionProfile")  # the reference's IllegalArgumentException
     N.check(rc, None, "profile_keys")

@@ -243,6 +243,12 @@ class SRTPEngine:
         flags = int(flags) | getattr(self, "_env_debug", 0)
         N.check(N.lib().srtp_engine_set_debug(self.h, flags), self.h, "set_debug")
 
+    def enable_aead(self, on: bool = True) -> None:
+        """srtp_engine_enable_aead: let new factories carry the RFC 7714 AES-GCM
+        policy (profile_policies("AEAD_AES_128_GCM" / "AEAD_AES_256_GCM")); off
+        on a new engine.  Existing GCM factories keep working when turned off."""
+        N.check(N.lib().srtp_engine_enable_aead(self.h, int(bool(on))), self.h, "enable_aead")
+
     def read_timing(self) -> dict:
         """{stage: (total ms, bundles)} since the last read (HIP events)."""
         ms = (C.c_double * len(N.STAGES))()
@@ -451,6 +457,10 @@ class SRTPDispatcher:
         st = N.Stats()
         self._chk(N.lib().srtp_dispatch_stats(self.h, C.byref(st)), "stats")
         return st.as_dict()
+
+    def enable_aead(self, on: bool = True) -> None:
+        """srtp_dispatch_enable_aead: SRTPEngine.enable_aead on every shard."""
+        self._chk(N.lib().srtp_dispatch_enable_aead(self.h, int(bool(on))), "enable_aead")
 
     def host_times(self) -> dict:
         """srtp_dispatch_host_times in ms (plan, pack, wait, scatter, total) and calls."""
