@@ -82,10 +82,12 @@ extern "C" {
  * with the switch on).  Either policy of a factory, or both, may be GCM.
  * Packets: SRTP header as AAD, ciphertext, 16-byte tag; SRTCP header(8),
  * ciphertext, tag, E|index word, the word being AAD too (RFC 7714 8-9;
- * statuses and lengths in srtp_gcm_packet_job).  Bundles only
- * (srtp_transform_*, srtp_pipeline_*, srtp_dispatch_*): the per-packet paths
- * (srtp_aggregator_*, srtp_queue_*, srtp_rawpacket_*) leave 16 bytes of trailer
- * room, four short of GCM SRTCP.  Beside it: the key derivation of RFC 7714 11
+ * statuses and lengths in srtp_gcm_packet_job).  Bundles
+ * (srtp_transform_*, srtp_pipeline_*, srtp_dispatch_*) and the per-packet paths
+ * (srtp_aggregator_*, srtp_queue_*, srtp_rawpacket_*) alike: an aggregator or
+ * RawPacket batch created after the switch was turned on leaves 20 bytes of
+ * trailer room, what GCM SRTCP appends (srtp_engine_trailer_room).  Still
+ * closed to GCM key sets: k_small, its direct mode and the split path.  Beside it: the key derivation of RFC 7714 11
  * (srtp_derive_session_keys_for), the AEAD on the host (srtp_aes_gcm) and as a
  * stateless GPU batch (srtp_aes_gcm_device), the dispatcher's may-throw test
  * (srtp_packet_may_throw, tag_mask bit 16), and the DTLS-SRTP ids
@@ -258,6 +260,15 @@ int srtp_engine_stats(srtp_engine *e, srtp_stats *out);
  * one launch, which such bundles take under the split path's key-set rule);
  * FORCE_WIDE and NO_WIDE keep them off it too. */
 #define SRTP_DEBUG_NO_SMALL 0x8u
+/* The AES-GCM passes of a bundle of up to srtp_gcm_wave_max() packets run a wave
+ * per packet (k_gcm_wave: GHASH as a sum over the powers of H, a block per
+ * lane), larger ones a lane per packet (k_gcm).  SRTP_DEBUG_NO_GCM_WAVE always
+ * takes the lane kernel, SRTP_DEBUG_FORCE_GCM_WAVE always the wave kernel (so
+ * that every parity case reaches it; A/B measurements).  Results must not
+ * change. */
+#define SRTP_DEBUG_NO_GCM_WAVE 0x10u
+#define SRTP_DEBUG_FORCE_GCM_WAVE 0x20u
+int32_t srtp_gcm_wave_max(void);
 int srtp_engine_set_debug(srtp_engine *e, uint32_t flags);
 /* The AES-GCM switch (RFC 7714 profiles, see SRTP_AESGCM_ENCRYPTION): off on a
  * new engine.  While on, srtp_factory_create accepts the GCM policy shape for
@@ -265,6 +276,17 @@ int srtp_engine_set_debug(srtp_engine *e, uint32_t flags);
  * factories and leaves existing ones working.  An engine that holds a GCM
  * factory runs every bundle on the multi-kernel path. */
 int srtp_engine_enable_aead(srtp_engine *e, int32_t on);
+/* The room, in bytes, that the per-packet paths leave behind a packet for
+ * protect's trailer: 16 (SRTCP's E|index word and a 12-byte tag), or 20 when
+ * `aead` is non-zero (GCM SRTCP: a 16-byte tag and the word).
+ * srtp_engine_trailer_room: that of the engine's AES-GCM switch as it stands
+ * (16 for NULL).  An aggregator (and so every queue on it) and a RawPacket
+ * batch sample it once, when they are created: turn the switch on before
+ * creating them.  One created earlier keeps 16, and protecting a GCM SRTCP
+ * packet through it answers SRTP_STATUS_ERR_CAPACITY; an engine without the
+ * switch packs exactly the bundles it always did. */
+int32_t srtp_trailer_room(int32_t aead);
+int32_t srtp_engine_trailer_room(srtp_engine *e);
 
 /* Context-state export / import: lets a stream's ROC, s_l,
  * replay window and SRTCP indices follow it to another engine or GPU (SSRC
@@ -432,8 +454,9 @@ int srtp_pipeline_submit_gather(srtp_pipeline *pl, int32_t slot, int32_t reverse
  * :268-300,652-830 send; each a 1-element array through
  * SinglePacketTransformer.java:121-216).
  *
- * srtp_aggregator_submit copies one packet (len bytes; protect leaves 16
- * bytes of trailer room) into the open bundle of its direction; a bundle is
+ * srtp_aggregator_submit copies one packet (len bytes; protect leaves the
+ * aggregator's trailer room behind it, srtp_aggregator_trailer_room: 16 bytes,
+ * or 20 on an engine with AES-GCM on) into the open bundle of its direction; a bundle is
  * sealed when it holds max_packets packets or max_bytes bytes, when its oldest
  * packet has waited deadline_us, or on srtp_aggregator_flush.  Sealed bundles
  * run in sealing order; when one completes, `cb` is called (on the
@@ -506,6 +529,11 @@ int srtp_aggregator_transform(srtp_aggregator *a, int32_t reverse, int32_t tid, 
  * (srtp_transformer_info on the first shard). */
 int srtp_aggregator_transformer_info(srtp_aggregator *a, int32_t t, int32_t *kind,
                                      int32_t *fwd_rtcp_tag_len);
+/* The trailer room the aggregator sampled when it was created
+ * (srtp_engine_trailer_room of its engine, or of its dispatcher's shards): what
+ * srtp_aggregator_submit adds to a protect packet's length for its region, and
+ * what srtp_rawpacket_transform_one / srtp_rawpacket_submit use on it. */
+int32_t srtp_aggregator_trailer_room(srtp_aggregator *a);
 
 /* Completion queues: the asynchronous per-packet call.  The
  * reference's connectors already queue: RTPConnectorOutputStream.write hands
@@ -721,8 +749,8 @@ int srtp_rawpacket_batch_set_aggregator(srtp_rawpacket_batch *b, srtp_aggregator
  * of buf_len bytes holds the packet at offset with *length bytes; *status,
  * *length and the bytes in buf are updated in place; *need_len != 0 where the
  * reference reallocates (RawPacket.append / grow), the result then being the
- * first *need_len bytes of grow, which must hold grow_cap >= *length + 16
- * bytes and at least the bytes from offset to the end of buf (min 65535).
+ * first *need_len bytes of grow, which must hold grow_cap >= *length + the
+ * aggregator's trailer room (16 or 20) bytes and at least the bytes from offset to the end of buf (min 65535).
  * SRTP_STATUS_ERR_MALFORMED: the reference throws (the packet keeps its
  * partial mutation); the caller rethrows. */
 int srtp_rawpacket_transform_one(srtp_aggregator *a, int32_t reverse, int32_t tid, uint8_t *buf,
@@ -810,6 +838,22 @@ int srtp_aes_gcm_device(srtp_engine *e, int32_t open, const uint8_t *key, int32_
                         uint8_t *seg, const uint32_t *off, const uint32_t *aad_len,
                         const uint32_t *len, const uint8_t *iv, uint8_t *tag, int32_t *result,
                         uint32_t n, void *stream);
+/* The same with flags (0: srtp_aes_gcm_device itself).  SRTP_GCM_BATCH_WAVE
+ * gives each packet a wave instead of a lane (k_gcm_aead_wave, the stateless
+ * twin of the engine's k_gcm_wave): GHASH as a sum over the powers H^1..H^64,
+ * which then travel in the kernel's arguments too, a block per lane, and the
+ * AES-CTR blocks spread over the lanes.  Same arguments, same results to the
+ * byte; SRTP_EINVAL for any other flag bit. */
+#define SRTP_GCM_BATCH_WAVE 0x1u
+int srtp_aes_gcm_device_ex(srtp_engine *e, int32_t open, const uint8_t *key, int32_t key_len,
+                           uint8_t *seg, const uint32_t *off, const uint32_t *aad_len,
+                           const uint32_t *len, const uint8_t *iv, uint8_t *tag, int32_t *result,
+                           uint32_t n, uint32_t flags, void *stream);
+/* Host GF(2^128) arithmetic in GCM's bit order, for tests: out = a * b (16-byte
+ * blocks as GHASH takes them; SP 800-38D algorithm 1), and out[16 k ..] =
+ * h^(k + 1) for k = 0..63, the powers the wave kernels multiply by. */
+int srtp_gf128_mul(const uint8_t a[16], const uint8_t b[16], uint8_t out[16]);
+int srtp_gcm_hpowers(const uint8_t h[16], uint8_t out[1024]);
 
 /* The stateless geometry of one packet under the AES-GCM profiles (host only;
  * the function the GPU passes take every offset from): the status the lengths

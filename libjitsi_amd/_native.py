@@ -31,6 +31,9 @@ DEBUG_FORCE_CHAIN_STALL = 0x1
 DEBUG_FORCE_WIDE = 0x2  # every bundle on the split path (k_ctr_wide + k_mac_wide)
 DEBUG_NO_WIDE = 0x4     # every bundle on the fused kernels
 DEBUG_NO_SMALL = 0x8    # bundles of up to 255 packets off k_small (one launch per bundle)
+DEBUG_NO_GCM_WAVE = 0x10     # the AES-GCM passes always a lane per packet (k_gcm)
+DEBUG_FORCE_GCM_WAVE = 0x20  # ... always a wave per packet (k_gcm_wave)
+GCM_BATCH_WAVE = 0x1         # srtp_aes_gcm_device_ex: a wave per packet
 ABI_VERSION = 3
 AGG_SEAL_IDLE = 0x1
 PKT_FLAG_DISCARD, PKT_FLAG_SILENCE, PKT_FLAG_SKIP = 0x2, 0x4, 0x80000000
@@ -75,6 +78,8 @@ EXPORTED = [
     "srtp_pipeline_query", "srtp_aes_gcm_device",
     "srtp_engine_enable_aead", "srtp_gcm_packet_job", "srtp_dtls_profile_keys_ex",
     "srtp_dispatch_enable_aead",
+    "srtp_aes_gcm_device_ex", "srtp_gf128_mul", "srtp_gcm_hpowers", "srtp_gcm_wave_max",
+    "srtp_trailer_room", "srtp_engine_trailer_room", "srtp_aggregator_trailer_room",
 ]
 STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 
@@ -273,6 +278,17 @@ def lib() -> C.CDLL:
     L.srtp_dtls_profile_keys.argtypes = [i32, C.c_char_p, i32, C.POINTER(DtlsKeys)]
     L.srtp_dtls_profile_keys_ex.argtypes = [i32, C.c_char_p, i32, C.POINTER(DtlsKeysEx), u32]
     L.srtp_engine_enable_aead.argtypes = [vp, i32]
+    L.srtp_aes_gcm_device_ex.argtypes = [vp, i32, C.c_char_p, i32, vp, vp, vp, vp, vp, vp, vp, u32, u32, vp]
+    L.srtp_gf128_mul.argtypes = [C.c_char_p, C.c_char_p, pu8]
+    L.srtp_gcm_hpowers.argtypes = [C.c_char_p, pu8]
+    L.srtp_gcm_wave_max.argtypes = []
+    L.srtp_gcm_wave_max.restype = i32
+    L.srtp_trailer_room.argtypes = [i32]
+    L.srtp_trailer_room.restype = i32
+    L.srtp_engine_trailer_room.argtypes = [vp]
+    L.srtp_engine_trailer_room.restype = i32
+    L.srtp_aggregator_trailer_room.argtypes = [vp]
+    L.srtp_aggregator_trailer_room.restype = i32
     L.srtp_dispatch_enable_aead.argtypes = [vp, i32]
     L.srtp_gcm_packet_job.argtypes = [i32, i32, i32, i32, i32, u32, i32, C.POINTER(GcmJob)]
     L.srtp_dtls_transformer_create.argtypes = [vp, i32, i32, i32, C.c_char_p, i32, pi32, pi32]

@@ -319,6 +319,9 @@ struct srtp_aggregator {
     uint32_t blk = kBlock;      // entries per block (max_packets if smaller)
     uint32_t n_blk = 0;         // blocks per slot
     uint32_t blk_bytes = 0;     // default byte range of a block
+    // the room protect gets behind a submitted packet: srtp_engine_trailer_room
+    // of the engine(s), sampled once at creation (16, or 20 with AES-GCM on)
+    uint32_t room = 16;
 
     std::mutex mu;
     std::condition_variable cv_flush; // the flusher: a new deadline
@@ -547,7 +550,7 @@ void place_parked_locked(srtp_aggregator *a, Lane &ln, uint32_t lane) {
         Parked &pk = ln.parked.front();
         const int dir = pk.reverse ? 1 : 0;
         const uint32_t len = (uint32_t)pk.pkt.size();
-        const uint32_t cap = pk.reverse ? len : len + 16u;
+        const uint32_t cap = pk.reverse ? len : len + a->room;
         const size_t need = need_of(cap);
         int s;
         uint32_t i;
@@ -920,6 +923,7 @@ int create(srtp_dispatch *d, srtp_engine *const *engines, size_t n_lanes, const 
     a->n_blk = o.max_packets / a->blk;
     a->blk_bytes = (uint32_t)std::max<size_t>(64, (o.max_bytes / a->n_blk) & ~(size_t)15);
     a->n_kinds = eo.max_transformers;
+    for (size_t l = 0; l < n_lanes; l++) a->room = std::max(a->room, (uint32_t)srtp_engine_trailer_room(engines[l]));
     a->kinds.reset(new (std::nothrow) std::atomic<int32_t>[a->n_kinds]);
     if (!a->kinds) {
         delete a;
@@ -1113,10 +1117,11 @@ int srtp_aggregator_create_dispatch(srtp_dispatch *d, const srtp_aggregator_opts
 
 int srtp_aggregator_submit(srtp_aggregator *a, int32_t reverse, int32_t tid, const uint8_t *pkt,
                            uint32_t len, uint32_t flags, uint64_t cookie) {
-    if (!a || !a->cb || (!pkt && len) || len > 65535u - 16u) return SRTP_EINVAL;
-    // protect appends up to 16 bytes (SRTCP E|index + a 12-byte tag): the
-    // in-place form of RawPacket.append / grow; unprotect only shrinks
-    const uint32_t cap = reverse ? len : len + 16u;
+    if (!a || !a->cb || (!pkt && len) || len > 65535u - a->room) return SRTP_EINVAL;
+    // protect appends up to 16 bytes (SRTCP E|index + a 12-byte tag; 20 on an
+    // engine with AES-GCM on: a 16-byte tag + E|index): the in-place form of
+    // RawPacket.append / grow; unprotect only shrinks
+    const uint32_t cap = reverse ? len : len + a->room;
     return submit_entry(a, reverse, tid, pkt, len, len, cap, flags, cookie, nullptr);
 }
 
@@ -1166,6 +1171,8 @@ int srtp_aggregator_transform(srtp_aggregator *a, int32_t reverse, int32_t tid, 
     *out_len = r.w.len;
     return SRTP_OK;
 }
+
+int32_t srtp_aggregator_trailer_room(srtp_aggregator *a) { return a ? (int32_t)a->room : 16; }
 
 int srtp_aggregator_transformer_info(srtp_aggregator *a, int32_t t, int32_t *kind, int32_t *fwd_rtcp_tag_len) {
     if (!a || t < 0 || (uint32_t)t >= a->n_kinds) return SRTP_EINVAL;

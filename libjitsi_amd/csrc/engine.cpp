@@ -37,6 +37,7 @@ struct srtp_engine {
     uint32_t n_ext = 0;           // k_ext key sets created (F8, AES-256, Twofish, Skein): k_ext runs only when > 0
     uint32_t n_skein = 0;         // Skein-MAC key sets created: k_skein runs only when > 0
     GcmKeys *d_gcmkeys = nullptr; // 1 per key set, allocated with the first AES-GCM factory
+    GcmPow *d_gcmpow = nullptr;   // beside it: the powers of each GCM key set's H (k_gcm_wave)
     uint32_t n_gcm = 0;           // AES-GCM key sets created: k_gcm and the walk's GCM instances only when > 0
     bool aead = false;            // srtp_engine_enable_aead: new factories may carry the GCM policy
     uint32_t n_not_wide = 0;      // key sets the split path cannot run (not AES-CM / NULL cipher + HMAC-SHA1)
@@ -202,13 +203,13 @@ int master_key_len(const srtp_policy *pol) {
 // kernels that do not know the mark take their NULL / NULL path on its
 // packets; the keys proper go to the GcmKeys table (k_gcm, the walk's re-check).
 void build_keyset_gcm(const uint8_t *mk, const uint8_t *ms, bool rtcp, const srtp_policy *pol, KeySet *ks,
-                      GcmKeys *gk) {
+                      GcmKeys *gk, GcmPow *gp) {
     memset(ks, 0, sizeof *ks);
     memset(gk, 0, sizeof *gk);
     uint8_t enc[32], salt[14];
     derive_session_keys_gcm(mk, pol->enc_key_len, ms, rtcp, enc, salt);
     GcmKeyArg ka;
-    gcm_key_arg(enc, pol->enc_key_len, &ka);
+    gcm_key_arg_pow(enc, pol->enc_key_len, &ka, gp->pow);
     memcpy(gk->rk, ka.rk, sizeof gk->rk);
     gk->nr = ka.nr;
     memcpy(gk->htab, ka.htab, sizeof gk->htab);
@@ -582,13 +583,15 @@ void srtp_engine_destroy(srtp_engine *e) {
         (void)hipMemset(e->d_skkeys, 0, (size_t)e->max_keysets * sizeof(SkeinKeys));
     if (e->d_gcmkeys)
         (void)hipMemset(e->d_gcmkeys, 0, (size_t)e->max_keysets * sizeof(GcmKeys));
+    if (e->d_gcmpow)
+        (void)hipMemset(e->d_gcmpow, 0, (size_t)e->max_keysets * sizeof(GcmPow));
     free_scratch(e);
     for (auto &m : e->marks) {
         (void)hipEventDestroy(m.a);
         (void)hipEventDestroy(m.b);
     }
     for (auto ev : e->event_pool) (void)hipEventDestroy(ev);
-    void *ptrs[] = {e->d_keysets, e->d_extkeys, e->d_tfkeys, e->d_skkeys, e->d_gcmkeys, e->d_factories, e->d_transformers, e->d_ctx_keys, e->d_ctx,
+    void *ptrs[] = {e->d_keysets, e->d_extkeys, e->d_tfkeys, e->d_skkeys, e->d_gcmkeys, e->d_gcmpow, e->d_factories, e->d_transformers, e->d_ctx_keys, e->d_ctx,
                     e->d_far, e->e_min, e->ctl, e->d_count, e->d_counters, e->h_seg, e->h_off, e->h_len,
                     e->h_cap, e->h_flags, e->h_status, e->h_tids};
     for (void *p : ptrs) dfree(p);
@@ -623,28 +626,36 @@ int srtp_factory_create(srtp_engine *e, int32_t sender, const uint8_t *mk, int32
     std::vector<TwofishKeys> tf(4);
     SkeinKeys sk[2];
     GcmKeys gk[2];
+    GcmPow gp[2];
     memset(gk, 0, sizeof gk);
+    memset(gp, 0, sizeof gp);
     for (int i = 0; i < 2; i++) {
         if (gcm[i]) {
             memset(&f8[i], 0, sizeof f8[i]);
             std::fill(tf.begin() + 2 * i, tf.begin() + 2 * i + 2, TwofishKeys{});
             memset(&sk[i], 0, sizeof sk[i]);
-            build_keyset_gcm(mk, ms, i == 1, pols[i], &ks[i], &gk[i]);
+            build_keyset_gcm(mk, ms, i == 1, pols[i], &ks[i], &gk[i], &gp[i]);
         } else {
             build_keyset(mk, ms, i == 1, pols[i], &ks[i], &f8[i], &tf[2 * i], &sk[i]);
         }
     }
     if (gcm[0] || gcm[1]) {
-        if (!e->d_gcmkeys && dalloc(&e->d_gcmkeys, (size_t)e->max_keysets) != hipSuccess) {
+        const bool first = !e->d_gcmpow;
+        if ((!e->d_gcmkeys && dalloc(&e->d_gcmkeys, (size_t)e->max_keysets) != hipSuccess) ||
+            (first && (dalloc(&e->d_gcmpow, (size_t)e->max_keysets) != hipSuccess ||
+                       hipMemset(e->d_gcmpow, 0, (size_t)e->max_keysets * sizeof(GcmPow)) != hipSuccess))) {
             memset(gk, 0, sizeof gk);
+            memset(gp, 0, sizeof gp);
             return fail(e, SRTP_ENOMEM, "AES-GCM key table");
         }
         // an enqueued bundle may hold the table pointer it was given: null before
         // the first GCM factory, and then it runs no GCM pass
         HIPCHK(e, hipMemcpy(e->d_gcmkeys + e->n_keysets, gk, sizeof gk, hipMemcpyHostToDevice));
+        HIPCHK(e, hipMemcpy(e->d_gcmpow + e->n_keysets, gp, sizeof gp, hipMemcpyHostToDevice));
         e->n_gcm += (uint32_t)gcm[0] + (uint32_t)gcm[1];
     }
     memset(gk, 0, sizeof gk);
+    memset(gp, 0, sizeof gp);
     const bool any_skein = srtp_pol->auth_type == SRTP_SKEIN_AUTHENTICATION ||
                            srtcp_pol->auth_type == SRTP_SKEIN_AUTHENTICATION;
     if (any_skein) {
@@ -806,6 +817,8 @@ static int transform_locked(srtp_engine *e, int32_t reverse, const int32_t *tids
     a.skkeys = e->d_skkeys;
     a.has_skein = e->n_skein ? 1 : 0;
     a.gcmkeys = e->d_gcmkeys;
+    a.gcmpow = e->d_gcmpow;
+    a.gcm_route = (e->dbg & SRTP_DEBUG_NO_GCM_WAVE) ? kGcmRouteLane : (e->dbg & SRTP_DEBUG_FORCE_GCM_WAVE) ? kGcmRouteWave : 0;
     a.has_gcm = e->n_gcm ? 1 : 0;
     a.factories = e->d_factories;
     a.transformers = e->d_transformers;
@@ -1266,7 +1279,8 @@ int32_t srtp_device_count(void) {
 }
 
 int srtp_engine_set_debug(srtp_engine *e, uint32_t flags) {
-    if (!e || (flags & ~(SRTP_DEBUG_FORCE_CHAIN_STALL | SRTP_DEBUG_FORCE_WIDE | SRTP_DEBUG_NO_WIDE | SRTP_DEBUG_NO_SMALL)))
+    if (!e || (flags & ~(SRTP_DEBUG_FORCE_CHAIN_STALL | SRTP_DEBUG_FORCE_WIDE | SRTP_DEBUG_NO_WIDE | SRTP_DEBUG_NO_SMALL |
+                        SRTP_DEBUG_NO_GCM_WAVE | SRTP_DEBUG_FORCE_GCM_WAVE)))
         return SRTP_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     e->dbg = flags;
@@ -1355,12 +1369,34 @@ int srtp_aes_gcm_device(srtp_engine *e, int32_t open, const uint8_t *key, int32_
                         uint8_t *seg, const uint32_t *off, const uint32_t *aad_len,
                         const uint32_t *len, const uint8_t *iv, uint8_t *tag, int32_t *result,
                         uint32_t n, void *stream) {
+    return srtp_aes_gcm_device_ex(e, open, key, key_len, seg, off, aad_len, len, iv, tag, result, n, 0u, stream);
+}
+
+int srtp_aes_gcm_device_ex(srtp_engine *e, int32_t open, const uint8_t *key, int32_t key_len,
+                           uint8_t *seg, const uint32_t *off, const uint32_t *aad_len,
+                           const uint32_t *len, const uint8_t *iv, uint8_t *tag, int32_t *result,
+                           uint32_t n, uint32_t flags, void *stream) {
     if (!e) return SRTP_EINVAL;
     std::lock_guard<std::mutex> lk(e->mu);
     const int chk = gcm_batch_check(key, key_len, seg, off, aad_len, len, iv, tag, result, open != 0, n);
     if (chk < 0) return fail(e, SRTP_EINVAL, "a key of 16 or 32 bytes and no null buffer");
+    if (flags & ~(uint32_t)SRTP_GCM_BATCH_WAVE) return fail(e, SRTP_EINVAL, "unknown AES-GCM batch flag");
     if (chk > 0) return SRTP_OK;
     GUARD(e);
+    if (flags & SRTP_GCM_BATCH_WAVE) { // a wave per packet: the batch plus the powers of H
+        GcmBatchWave w{};
+        gcm_key_arg_pow(key, key_len, &w.b.key, w.pow);
+        w.b.seg = seg; w.b.off = off; w.b.aad_len = aad_len; w.b.len = len;
+        w.b.iv = iv; w.b.tag = tag; w.b.result = result;
+        w.b.n = n;
+        w.b.open = open ? 1 : 0;
+        const hipError_t err = launch_gcm_aead_wave(w, (hipStream_t)stream);
+        memset(&w.b.key, 0, sizeof w.b.key);
+        memset(w.pow, 0, sizeof w.pow);
+        if (err != hipSuccess)
+            return fail(e, SRTP_EDEVICE, std::string("k_gcm_aead_wave: ") + hipGetErrorString(err));
+        return SRTP_OK;
+    }
     GcmBatch g{};
     gcm_key_arg(key, key_len, &g.key);
     g.seg = seg; g.off = off; g.aad_len = aad_len; g.len = len;
@@ -1372,6 +1408,45 @@ int srtp_aes_gcm_device(srtp_engine *e, int32_t open, const uint8_t *key, int32_
     memset(&g.key, 0, sizeof g.key);
     if (err != hipSuccess) return fail(e, SRTP_EDEVICE, std::string("k_gcm_aead: ") + hipGetErrorString(err));
     return SRTP_OK;
+}
+
+int srtp_gf128_mul(const uint8_t a[16], const uint8_t b[16], uint8_t out[16]) {
+    if (!a || !b || !out) return SRTP_EINVAL;
+    auto be = [](const uint8_t *p) {
+        uint64_t v = 0;
+        for (int i = 0; i < 8; i++) v = (v << 8) | p[i];
+        return v;
+    };
+    const uint64_t x[2] = {be(a + 8), be(a)}, y[2] = {be(b + 8), be(b)};
+    uint64_t z[2];
+    gf128_mul(x, y, z);
+    for (int i = 0; i < 8; i++) {
+        out[i] = (uint8_t)(z[1] >> (56 - 8 * i));
+        out[8 + i] = (uint8_t)(z[0] >> (56 - 8 * i));
+    }
+    return SRTP_OK;
+}
+
+int srtp_gcm_hpowers(const uint8_t h[16], uint8_t out[1024]) {
+    if (!h || !out) return SRTP_EINVAL;
+    uint64_t pw[kGcmPowers][2];
+    gcm_hpowers(h, pw);
+    for (int k = 0; k < kGcmPowers; k++)
+        for (int i = 0; i < 8; i++) {
+            out[16 * k + i] = (uint8_t)(pw[k][1] >> (56 - 8 * i));
+            out[16 * k + 8 + i] = (uint8_t)(pw[k][0] >> (56 - 8 * i));
+        }
+    return SRTP_OK;
+}
+
+int32_t srtp_gcm_wave_max(void) { return (int32_t)kGcmWaveMax; }
+
+int32_t srtp_trailer_room(int32_t aead) { return (int32_t)trailer_room(aead); }
+
+int32_t srtp_engine_trailer_room(srtp_engine *e) {
+    if (!e) return (int32_t)trailer_room(0);
+    std::lock_guard<std::mutex> g(e->mu);
+    return (int32_t)trailer_room(e->aead ? 1 : 0);
 }
 
 int srtp_engine_enable_aead(srtp_engine *e, int32_t on) {

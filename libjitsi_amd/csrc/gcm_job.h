@@ -42,6 +42,12 @@ constexpr int kGcmStDropAuth = 2, kGcmStCapacity = 5, kGcmStMalformed = 6, kGcmS
               kGcmStInternal = 10;
 constexpr uint32_t kGcmFlagNoDecipher = 0x2u | 0x4u; // SRTP_PKT_FLAG_DISCARD | _SILENCE
 
+// The room behind a packet that protect may need on the per-packet paths
+// (aggregator, queue, RawPacket batch): SRTCP's E|index word and a 12-byte
+// tag, or, on an engine whose AES-GCM switch is on, GCM SRTCP's 16-byte tag
+// and the word (the SRTCP protect rule below).
+SRTP_GCM_HD inline uint32_t trailer_room(int aead) { return aead ? (uint32_t)kGcmTag + 4u : 16u; }
+
 struct GcmJob {
     int32_t status;   // kGcmNoStatus, or the status the lengths alone decide (then no range is valid)
     int32_t new_len;  // the length the packet leaves with (under `status`, or when accepted)

@@ -405,6 +405,26 @@ void gcm_mult_xor(const uint64_t tab[16][2], uint8_t y[16], const uint8_t x[16])
     put_be64(y + 8, zl);
 }
 
+void gf128_mul(const uint64_t a[2], const uint64_t b[2], uint64_t out[2]) {
+    uint64_t zl = 0, zh = 0, vl = b[0], vh = b[1];
+    for (int i = 0; i < 128; i++) { // a's bits from the first byte's top one down
+        const uint64_t bit = ((i < 64 ? a[1] : a[0]) >> (63 - (i & 63))) & 1;
+        zl ^= vl & (0 - bit);
+        zh ^= vh & (0 - bit);
+        const uint64_t t = (vl & 1) ? 0xe100000000000000ull : 0;
+        vl = (vh << 63) | (vl >> 1);
+        vh = (vh >> 1) ^ t;
+    }
+    out[0] = zl;
+    out[1] = zh;
+}
+
+void gcm_hpowers(const uint8_t h[16], uint64_t out[kGcmPowers][2]) {
+    out[0][0] = be64(h + 8);
+    out[0][1] = be64(h);
+    for (int k = 1; k < kGcmPowers; k++) gf128_mul(out[k - 1], out[0], out[k]);
+}
+
 bool aes_gcm(bool open, const uint32_t *rk, int nr, const uint8_t iv[12], const uint8_t *aad,
              size_t aad_len, uint8_t *data, size_t len, uint8_t tag[16]) {
     uint8_t h[16] = {0}, y[16] = {0}, blk[16], ctr[16], ek0[16];
@@ -461,6 +481,14 @@ void gcm_key_arg(const uint8_t *key, int key_len, GcmKeyArg *out) {
     out->nr = aes_expand_le(key, key_len, out->rk);
     aes_encrypt_block_nr(out->rk, out->nr, h, h);
     gcm_htable(h, out->htab);
+    memset(h, 0, sizeof h);
+}
+
+void gcm_key_arg_pow(const uint8_t *key, int key_len, GcmKeyArg *out, uint64_t pow[kGcmPowers][2]) {
+    uint8_t h[16] = {0};
+    gcm_key_arg(key, key_len, out);
+    aes_encrypt_block_nr(out->rk, out->nr, h, h);
+    gcm_hpowers(h, pow);
     memset(h, 0, sizeof h);
 }
 

@@ -68,6 +68,14 @@ void skein512_mac(const uint8_t *key, int key_len, int out_bits, const uint8_t *
 void gcm_htable(const uint8_t h[16], uint64_t tab[16][2]);
 // y = (y ^ x) * H with that table (y, x: 16 bytes).
 void gcm_mult_xor(const uint64_t tab[16][2], uint8_t y[16], const uint8_t x[16]);
+// The general product a * b in GF(2^128) (SP 800-38D algorithm 1), elements as
+// {low, high} halves in the bit order gcm_htable's entries have.
+void gf128_mul(const uint64_t a[2], const uint64_t b[2], uint64_t out[2]);
+// out[k] = H^(k + 1), k = 0..63, as such halves: with them GHASH is the
+// polynomial sum X_1 H^T + ... + X_T H^1, 64 terms at a time (k_gcm_wave;
+// GcmPow, GcmBatchWave::pow).
+constexpr int kGcmPowers = 64;
+void gcm_hpowers(const uint8_t h[16], uint64_t out[kGcmPowers][2]);
 // Seal (open = false) or open data[0, len) in place under the expanded key
 // rk / nr; tag[16] is written (seal) or compared (open: returns false on a
 // mismatch and leaves data untouched).
@@ -76,6 +84,8 @@ bool aes_gcm(bool open, const uint32_t *rk_le, int nr, const uint8_t iv[12], con
 // The key block of the stateless GPU batch (srtp_aes_gcm_device): the expanded
 // key (key_len 16 or 32) and gcm_htable(E_K(0^128)); every other byte zero.
 void gcm_key_arg(const uint8_t *key, int key_len, GcmKeyArg *out);
+// ... and with it gcm_hpowers(E_K(0^128)), for the wave-per-packet batch.
+void gcm_key_arg_pow(const uint8_t *key, int key_len, GcmKeyArg *out, uint64_t pow[kGcmPowers][2]);
 // The argument rules of srtp_aes_gcm_device after its engine test: -1 for a
 // missing key or a key_len other than 16 / 32 (whatever n is); else 1 for
 // n == 0 (nothing to launch, the arrays are not looked at); else -1 when an

@@ -43,6 +43,9 @@ struct srtp_rawpacket_batch {
     // srtp_rawpacket_batch_set_aggregator: small arrays that cannot throw go
     // through this queue on the aggregator's lanes (shared bundles)
     srtp_aggregator *agg = nullptr;
+    // the trailer room of an element's region on protect: the engine's
+    // (srtp_engine_trailer_room) at creation
+    uint32_t room = 16;
     std::vector<srtp_completion> comps;
     bool via_queue = false;               // the last call took the queue
     std::vector<const uint8_t *> res_ptr; // its results (srtp_rawpacket_result)
@@ -67,8 +70,6 @@ struct srtp_rawpacket_batch {
 };
 
 namespace {
-
-constexpr uint32_t kTrailerRoom = 16; // SRTCP E|index (4) + a 12-byte tag: the most protect appends
 
 size_t region(uint32_t cap) { return ((size_t)cap + 15) & ~(size_t)15; }
 
@@ -132,10 +133,13 @@ int stage(srtp_rawpacket_batch *b, uint32_t n, size_t bytes) {
 
 // The region an element gets (RawPacket.isInvalid compares the length with
 // it): the buffer after the offset, plus room for the trailer on protect --
-// the in-place form of append / grow.  avail = the buffer's bytes after offset.
-uint32_t element_cap(int32_t reverse, uint32_t avail, uint32_t length) {
+// the in-place form of append / grow.  avail = the buffer's bytes after offset;
+// room = the most protect appends: SRTCP E|index (4) + a 12-byte tag, or 20
+// where the batch or aggregator was created on an engine with AES-GCM on
+// (srtp_engine_trailer_room).
+uint32_t element_cap(int32_t reverse, uint32_t avail, uint32_t length, uint32_t room) {
     const bool fits = length <= avail;
-    const uint64_t c = (fits && !reverse) ? std::max<uint64_t>(avail, (uint64_t)length + kTrailerRoom) : avail;
+    const uint64_t c = (fits && !reverse) ? std::max<uint64_t>(avail, (uint64_t)length + room) : avail;
     return (uint32_t)std::min<uint64_t>(c, 65535u);
 }
 
@@ -208,7 +212,7 @@ int submit_element(srtp_queue *q, int32_t reverse, int32_t tid, const uint8_t *b
     const uint32_t avail = offset <= buf_len ? buf_len - offset : 0u;
     if (length > avail || length > 65535u) // RawPacket.isInvalid: completes untouched
         return srtp_queue_submit(q, reverse, tid, nullptr, 0, std::min<uint32_t>(length, 65535u), 0, 0, cookie);
-    const uint32_t cap = element_cap(reverse, avail, length);
+    const uint32_t cap = element_cap(reverse, avail, length, (uint32_t)srtp_aggregator_trailer_room(srtp_queue_aggregator(q)));
     return srtp_queue_submit(q, reverse, tid, buf + offset, std::min(avail, cap), length, cap,
                              flags & (SRTP_PKT_FLAG_DISCARD | SRTP_PKT_FLAG_SILENCE), cookie);
 }
@@ -228,7 +232,7 @@ int transform_via_queue(srtp_rawpacket_batch *b, int32_t reverse, const int32_t 
         if (length[i] > avail) continue; // untouched
         int32_t kind = SRTP_KIND_RTP;
         if (srtp_aggregator_transformer_info(b->agg, tids ? tids[i] : tid, &kind, nullptr) != SRTP_OK) return 1;
-        const uint32_t cap = std::min(avail, element_cap(reverse, avail, length[i]));
+        const uint32_t cap = std::min(avail, element_cap(reverse, avail, length[i], (uint32_t)srtp_aggregator_trailer_room(b->agg)));
         if (srtp_packet_may_throw(kind, reverse, bufs[i] + offset[i], length[i], cap, fl, kTagsAny)) return 1;
     }
     // The queue lives for this call only: a queue outliving it would hold the
@@ -346,6 +350,7 @@ int srtp_rawpacket_batch_create(srtp_engine *e, srtp_rawpacket_batch **out) {
     srtp_rawpacket_batch *b = new (std::nothrow) srtp_rawpacket_batch();
     if (!b) return SRTP_ENOMEM;
     b->e = e;
+    b->room = (uint32_t)srtp_engine_trailer_room(e);
     *out = b;
     return SRTP_OK;
 }
@@ -355,6 +360,7 @@ int srtp_rawpacket_batch_create_dispatch(srtp_dispatch *d, srtp_rawpacket_batch 
     srtp_rawpacket_batch *b = new (std::nothrow) srtp_rawpacket_batch();
     if (!b) return SRTP_ENOMEM;
     b->d = d;
+    b->room = (uint32_t)srtp_engine_trailer_room(srtp_dispatch_engine(d, 0));
     *out = b;
     return SRTP_OK;
 }
@@ -397,7 +403,7 @@ int srtp_rawpacket_transform(srtp_rawpacket_batch *b, int32_t reverse, const int
             ccap[i] = 16;
         } else {
             avail[i] = offset[i] <= buf_len[i] ? buf_len[i] - offset[i] : 0u;
-            ccap[i] = element_cap(reverse, avail[i], length[i]);
+            ccap[i] = element_cap(reverse, avail[i], length[i], b->room);
         }
         bytes += region(ccap[i]);
     }
@@ -540,7 +546,7 @@ int srtp_rawpacket_transform_one(srtp_aggregator *a, int32_t reverse, int32_t ti
         *status = SRTP_STATUS_DROP_INVALID;
         return SRTP_OK;
     }
-    const uint32_t cap = element_cap(reverse, avail, old);
+    const uint32_t cap = element_cap(reverse, avail, old, (uint32_t)srtp_aggregator_trailer_room(a));
     if (grow_cap < cap) return SRTP_EINVAL;
     uint32_t nl = 0;
     int rc = srtp_aggregator_transform(a, reverse, tid, buf + offset, std::min(avail, cap), old, cap,

@@ -101,6 +101,8 @@ struct BundleArgs {
     // selects the walk's GCM instances and the k_gcm passes
     const GcmKeys *gcmkeys;
     int32_t has_gcm;
+    int32_t gcm_route;     // launch_gcm: 0 by bundle size (kGcmWaveMax), else kGcmRoute* (test hooks)
+    const GcmPow *gcmpow;  // [keysets] beside gcmkeys: the powers of H (k_gcm_wave)
 };
 
 // Layout of the sort's scratch (one allocation of sort_temp_bytes(n_max)).
@@ -138,6 +140,16 @@ hipError_t launch_skein(const BundleArgs &a, hipStream_t s);
 // the tag check under k_unprotect's ROC guess; mode 2 (unprotect, after
 // k_unprotect_fix): the accepted packets deciphered; mode 0 (protect, after
 // k_protect): sealed, tag and SRTCP's E|index word written.
+// A bundle of up to kGcmWaveMax packets takes k_gcm_wave, a wave per packet
+// (the per-packet paths' bundles), a larger one k_gcm, a lane per packet;
+// BundleArgs::gcm_route (SRTP_DEBUG_NO_GCM_WAVE / _FORCE_GCM_WAVE) overrides
+// the size rule.  8192: the largest size of the measured sweep (1 .. 8192
+// 1200-byte packets, profiles/gcm_wave/sweep.json) at which the wave route's
+// median lies below the lane route's by more than the lane route's spread,
+// protect and unprotect; it did at every size of the sweep, by 3.7-4.3x up to
+// 64 packets and by 6-18 % at 8192.
+constexpr uint32_t kGcmWaveMax = 8192u;
+constexpr int32_t kGcmRouteLane = 1, kGcmRouteWave = 2;
 hipError_t launch_gcm(const BundleArgs &a, int mode, hipStream_t s);
 hipError_t launch_walk(const BundleArgs &a, int limit_pass, hipStream_t s);
 hipError_t launch_protect(const BundleArgs &a, hipStream_t s);
@@ -200,6 +212,13 @@ struct GcmBatch {
 };
 // n > 0; needs upload_tables() on the current device (every engine does it)
 hipError_t launch_gcm_aead(const GcmBatch &g, hipStream_t s);
+// SRTP_GCM_BATCH_WAVE: the same batch a wave per packet (k_gcm_aead_wave), with
+// gcm_hpowers of the key's H by value too.
+struct GcmBatchWave {
+    GcmBatch b;
+    uint64_t pow[64][2];
+};
+hipError_t launch_gcm_aead_wave(const GcmBatchWave &g, hipStream_t s);
 // Upload the LE T-table used by the AES rounds (once per device).
 hipError_t upload_tables(const uint32_t te0[256]);
 

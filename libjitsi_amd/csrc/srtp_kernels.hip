@@ -27,6 +27,10 @@
 //              k_unprotect_fix, the seal after k_protect; every packet offset from
 //              gcm_packet_job (gcm_job.h).  Such an engine's walk runs in the GCM
 //              instances of k_walk (walk_one_gcm for those contexts' records).
+//   k_gcm_wave [the same, bundles of up to kGcmWaveMax packets: the per-packet
+//              paths'] the three passes with a wave per packet: GHASH as a sum
+//              over the powers of H (GcmPow), a block per lane, and the AES-CTR
+//              blocks spread over the lanes.
 //   k_protect  [protect] one lane per packet: fused AES-CM keystream + XOR +
 //              HMAC-SHA1 (one read and one write of the packet bytes).
 //   k_unprotect_fix [unprotect] statuses/lengths out; undoes/redoes the rare
@@ -36,6 +40,8 @@
 //   k_gcm_aead [srtp_aes_gcm_device] AES-GCM of a batch of packets under one
 //              key, a lane per packet (GHASH by a 4-bit table in LDS + AES-CTR);
 //              stateless, launched by no bundle.
+//   k_gcm_aead_wave [srtp_aes_gcm_device_ex, SRTP_GCM_BATCH_WAVE] the same batch
+//              with a wave per packet, k_gcm_wave's stateless twin.
 //
 // AES uses four little-endian T-tables replicated 32x in LDS (128 KB) so that
 // lane l only ever touches LDS bank (l & 31): conflict-free ds_read_b32 with a
@@ -5190,6 +5196,342 @@ __global__ __launch_bounds__(kGcmBlock) void k_gcm(BundleArgs a) {
     }
 }
 
+// ============================================================== k_gcm_wave
+// The same three passes with a wave per packet, for the small bundles of the
+// per-packet paths, where a lane per packet leaves one lane walking a serial
+// GHASH chain of a multiplication per block.  GHASH is a polynomial in H,
+//   Y = X_1 H^T ^ X_2 H^(T-1) ^ ... ^ X_T H,
+// so with the powers H^1 .. H^64 at hand (GcmPow, host gcm_hpowers) 64 blocks
+// are absorbed at once: lane l multiplies block l (lane 0: with the running
+// value XORed in) by H^(m - l), m <= 64 the blocks of the chunk, and the wave
+// XORs the products together.  A 1200-byte packet is a chain of two general
+// multiplications instead of 77 table ones.  The AES-CTR blocks spread over
+// the lanes likewise.
+
+// a * b in GF(2^128), halves in the field's big-endian bit order as
+// gcm_mult_xor has them: SP 800-38D algorithm 1, bit-serial and branch-free on
+// 32-bit words (v[0] the most significant).  Per bit of a: one v_bfe_i32 for
+// the mask, 4 x (v_and, v_xor) into z, 4 v_alignbit for v >> 1 and 3 for the
+// reduction: 16 VALU.  The ISA listing has four loops (one per word of a) of
+// 131 VALU instructions per 8 bits: 2096 per product, against about 630 for one
+// table multiplication of gcm_mult_xor -- and a 1200-byte packet needs 2 of
+// these in a row where the lane kernel needs 77 of those.
+__device__ __forceinline__ void gf128_mul(uint64_t ah, uint64_t al, uint64_t bh, uint64_t bl, uint64_t &zh,
+                                          uint64_t &zl) {
+    const uint32_t aw[4] = {(uint32_t)(ah >> 32), (uint32_t)ah, (uint32_t)(al >> 32), (uint32_t)al};
+    uint32_t v[4] = {(uint32_t)(bh >> 32), (uint32_t)bh, (uint32_t)(bl >> 32), (uint32_t)bl};
+    uint32_t z[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+#pragma unroll 8
+        for (int i = 31; i >= 0; i--) {
+            const uint32_t m = (uint32_t)((int32_t)(aw[w] << (31 - i)) >> 31); // bit i of the word, spread
+#pragma unroll
+            for (int k = 0; k < 4; k++) z[k] ^= v[k] & m;
+            const uint32_t r = (uint32_t)((int32_t)(v[3] << 31) >> 31) & 0xe1000000u;
+            v[3] = (v[2] << 31) | (v[3] >> 1);
+            v[2] = (v[1] << 31) | (v[2] >> 1);
+            v[1] = (v[0] << 31) | (v[1] >> 1);
+            v[0] = (v[0] >> 1) ^ r;
+        }
+    }
+    zh = ((uint64_t)z[0] << 32) | z[1];
+    zl = ((uint64_t)z[2] << 32) | z[3];
+}
+
+// x XORed over the wave's 64 lanes (all active), in every lane.
+__device__ __forceinline__ uint64_t wave_xor64(uint64_t x) {
+    uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        lo ^= (uint32_t)__shfl_xor((int)lo, d);
+        hi ^= (uint32_t)__shfl_xor((int)hi, d);
+    }
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// Block i of a packet's GHASH input as one list of na + nd + 1 blocks: the na
+// blocks of the AAD (with SRTCP's tail word spliced in behind the head bytes,
+// as gcm_absorb_aad does), the nd data blocks, the length block.  Reads only
+// bytes of [aad, aad + aad_len + len).
+__device__ __forceinline__ void gcm_list_block(const GcmPkt &j, int na, int nd, int i, uint64_t &xh, uint64_t &xl) {
+    if (i >= na + nd) {
+        xh = (uint64_t)(j.aad_len + j.tail_len) * 8ull;
+        xl = (uint64_t)j.len * 8ull;
+        return;
+    }
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (i < na) {
+        const int m = j.aad_len - 16 * i; // head bytes from this block on; > -4, as the tail reaches into the block
+        if (m > 0) gcm_load(j.aad + 16 * i, min(16, m), w);
+        if (j.tail_len) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int o = 4 * k - m; // tail byte t sits at block position m + t
+                if (o > -4 && o < 4) w[k] |= o >= 0 ? (j.tail >> (8 * o)) : (j.tail << (8 * -o));
+            }
+        }
+    } else {
+        const int b = i - na;
+        gcm_load(j.aad + j.aad_len + 16 * b, min(16, j.len - 16 * b), w);
+    }
+    xh = ((uint64_t)bswap(w[0]) << 32) | bswap(w[1]);
+    xl = ((uint64_t)bswap(w[2]) << 32) | bswap(w[3]);
+}
+
+// gcm_packet with the packet's wave instead of one lane: every argument is
+// wave-uniform, all 64 lanes are active, and tag[] (mask_out[]) comes out in
+// every lane.  pw: the key's 64 powers of H (GcmPow's words; LDS or global).
+// AES-CTR: in a step of 128 counter blocks lane l takes counters 1 + l and
+// 65 + l of the step, counter c ciphering data block c - 2 and counter 1 being
+// the tag mask (lane 0's first block of the first step).  Seal then hashes the
+// ciphertext it stored, in the list's lane alignment, not the counters': the
+// wave re-reads its own stores behind a walk_sync().
+template <int MODE, class Cipher>
+__device__ __forceinline__ void gcm_packet_wave(const Cipher &cipher, const uint32_t *pw, const GcmPkt &j,
+                                                uint32_t lane, uint32_t tag[4], uint32_t *mask_out = nullptr) {
+    uint8_t *data = j.aad + j.aad_len;
+    const int nb = (j.len + 15) >> 4;
+    uint32_t mask[4] = {0u, 0u, 0u, 0u};
+    if (MODE == kGcmVerify) { // only the mask block is wanted: every lane computes it
+        uint32_t x[4] = {j.iv[0], j.iv[1], j.iv[2], bswap(1u)};
+        uint32_t y[4] = {j.iv[0], j.iv[1], j.iv[2], bswap(2u)};
+        cipher.encrypt2(x, y);
+#pragma unroll
+        for (int k = 0; k < 4; k++) mask[k] = x[k];
+    } else {
+        for (int s0 = 0; s0 < nb + 1; s0 += 128) { // counters s0 + 1 .. s0 + 128, of 1 .. nb + 1
+            const uint32_t c0 = (uint32_t)s0 + 1u + lane, c1 = c0 + 64u;
+            uint32_t x[4] = {j.iv[0], j.iv[1], j.iv[2], bswap(c0)};
+            uint32_t y[4] = {j.iv[0], j.iv[1], j.iv[2], bswap(c1)};
+            cipher.encrypt2(x, y);
+            if (MODE == kGcmSeal && s0 == 0) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) mask[k] = (uint32_t)__shfl((int)x[k], 0);
+            }
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                const uint32_t *ks = u ? y : x;
+                const int b = (int)(u ? c1 : c0) - 2;
+                if (b >= 0 && b < nb) {
+                    const int m = min(16, j.len - 16 * b);
+                    uint32_t d[4];
+                    gcm_load(data + 16 * b, m, d);
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const int keep = m - 4 * k; // bytes of word k inside the data
+                        const uint32_t km = keep >= 4 ? ~0u : (keep <= 0 ? 0u : (1u << (8 * keep)) - 1u);
+                        d[k] = (d[k] ^ ks[k]) & km;
+                    }
+                    gcm_store(data + 16 * b, m, d);
+                }
+            }
+        }
+        if (MODE == kGcmDecipher) return;
+        walk_sync(); // the ciphertext just stored, before other lanes load it
+    }
+    const int na = (j.aad_len + j.tail_len + 15) >> 4, T = na + nb + 1;
+    uint64_t zh = 0ull, zl = 0ull;
+    for (int base = 0; base < T; base += 64) {
+        const int m = min(64, T - base);
+        uint64_t ph = 0ull, pl = 0ull;
+        if ((int)lane < m) {
+            uint64_t xh, xl;
+            gcm_list_block(j, na, nb, base + (int)lane, xh, xl);
+            if (lane == 0u) {
+                xh ^= zh;
+                xl ^= zl;
+            }
+            const uint4 hp = *reinterpret_cast<const uint4 *>(pw + 4 * (m - 1 - (int)lane)); // H^(m - lane)
+            gf128_mul(xh, xl, (uint64_t)hp.z | ((uint64_t)hp.w << 32), (uint64_t)hp.x | ((uint64_t)hp.y << 32), ph,
+                      pl);
+        }
+        zh = wave_xor64(ph);
+        zl = wave_xor64(pl);
+    }
+    if (MODE == kGcmVerify && mask_out) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) mask_out[k] = mask[k];
+    }
+    tag[0] = bswap((uint32_t)(zh >> 32)) ^ mask[0];
+    tag[1] = bswap((uint32_t)zh) ^ mask[1];
+    tag[2] = bswap((uint32_t)(zl >> 32)) ^ mask[2];
+    tag[3] = bswap((uint32_t)zl) ^ mask[3];
+}
+
+constexpr int kGcmWaveBlock = 256; // four waves, four packets, around one T-table image
+constexpr int kGcmPowWords = 256;  // one key's 64 powers of H
+
+// The stateless batch a wave per packet (srtp_aes_gcm_device_ex with
+// SRTP_GCM_BATCH_WAVE): k_gcm_aead's arguments and results, with the key's
+// powers of H by value too, staged in LDS behind the image as it stages htab.
+__global__ __launch_bounds__(kGcmWaveBlock) void k_gcm_aead_wave(GcmBatchWave g) {
+    __shared__ uint32_t s_te[kTeWords + kGcmPowWords]; // the image stays at LDS 0
+    {
+        // word threadIdx.x of the powers: the argument words are scalars, so a
+        // lane selects its own (once per workgroup of kGcmPowWords threads)
+        uint32_t v = 0u;
+#pragma unroll
+        for (int i = 0; i < kGcmPowWords; i++) {
+            const uint32_t wi = (uint32_t)(g.pow[i >> 2][(i >> 1) & 1] >> (32 * (i & 1)));
+            v = threadIdx.x == (unsigned)i ? wi : v;
+        }
+        s_te[kTeWords + threadIdx.x] = v;
+    }
+    fill_te4(s_te); // ends with a barrier: the powers above are visible too
+    const uint32_t i = blockIdx.x * (uint32_t)(kGcmWaveBlock / 64) + (threadIdx.x >> 6);
+    if (i >= g.b.n) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t *pw = s_te + kTeWords;
+    RoundKeys256 rk;
+#pragma unroll
+    for (int k = 0; k < 60; k++) rk.k[k] = sgpr(g.b.key.rk[k]);
+    const GcmBatchCipher cipher{reinterpret_cast<const char *>(s_te), te_base(), rk,
+                                sgpr((uint32_t)g.b.key.nr) == 14u};
+    GcmPkt j;
+    j.aad = g.b.seg + g.b.off[i];
+    j.aad_len = (int)g.b.aad_len[i];
+    j.len = (int)g.b.len[i];
+    const uint8_t *ivp = g.b.iv + 12 * (size_t)i;
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+        j.iv[k] = ld_u8(ivp + 4 * k) | (ld_u8(ivp + 4 * k + 1) << 8) | (ld_u8(ivp + 4 * k + 2) << 16) |
+                  (ld_u8(ivp + 4 * k + 3) << 24);
+    uint8_t *tagp = g.b.tag + 16 * (size_t)i;
+    uint32_t tag[4];
+    if (!g.b.open) {
+        gcm_packet_wave<kGcmSeal>(cipher, pw, j, lane, tag);
+        if (lane == 0u) gcm_store(tagp, 16, tag);
+        return;
+    }
+    uint32_t got[4];
+    gcm_packet_wave<kGcmVerify>(cipher, pw, j, lane, tag);
+    gcm_load(tagp, 16, got);
+    const bool ok = ((tag[0] ^ got[0]) | (tag[1] ^ got[1]) | (tag[2] ^ got[2]) | (tag[3] ^ got[3])) == 0u;
+    if (lane == 0u) g.b.result[i] = ok ? 0 : 1;
+    if (ok) gcm_packet_wave<kGcmDecipher>(cipher, pw, j, lane, tag);
+}
+
+// Packet p of GCM key set ks_u for pass MODE, as gcm_one prepares it (the same
+// steps in the same order, kept apart so that k_gcm compiles as it did): false
+// when the pass has nothing to do on it, else its geometry j, the AEAD's view
+// of it gp and its first byte pkt.  writer: the one lane of the packet's wave
+// that clears the packet's verify result.
+template <int MODE>
+__device__ __forceinline__ bool gcm_prep(const BundleArgs &a, uint32_t ks_u, uint32_t p, bool writer, GcmJob &j,
+                                         GcmPkt &gp, uint8_t *&pkt) {
+    const KeySet *ks = a.keysets + ks_u;
+    const GcmKeys *gk = a.gcmkeys + ks_u;
+    const bool rtp = sgpr((uint32_t)ks->kind) == (uint32_t)SRTP_KIND_RTP;
+    const int trailer = rtp ? kGcmTag : kGcmTag + 4;
+    const uint32_t cap_u = a.cap[p], len_u = a.len[p];
+    if (cap_u > 65535u || len_u > 65535u) return false; // k_parse refused such a packet
+    const int C = (int)cap_u;
+    // the length the packet came with: a.len still holds it before the walk;
+    // after the final statuses it holds the new one (status OK here)
+    const int L = MODE == kGcmVerify ? (int)len_u : MODE == kGcmSeal ? (int)len_u - trailer : (int)len_u + trailer;
+    if (MODE == kGcmVerify && writer) a.gok[2 * (size_t)p + 1] = 0u;
+    if (L < 12 || L > C) return false; // the job would say so too; no header byte is read before this
+    pkt = a.seg + a.off[p];
+    const uint32_t fl = a.flags ? a.flags[p] : 0u;
+    const uint32_t salt[3] = {sgpr(gk->salt[0]), sgpr(gk->salt[1]), sgpr(gk->salt[2])};
+    gp.aad = pkt;
+    if (rtp) {
+        const uint32_t w0 = *reinterpret_cast<const uint32_t *>(pkt);     // V/P/X/CC, M/PT, SEQ
+        const uint32_t w2 = *reinterpret_cast<const uint32_t *>(pkt + 8); // SSRC
+        const int32_t h = rtp_header_len(pkt, w0 & 0xffu, C);
+        j = gcm_packet_job(0, MODE == kGcmSeal ? 0 : 1, L, C, h, fl, 1);
+        if (j.status != kGcmNoStatus) return false;
+        const uint32_t roc = MODE == kGcmVerify ? a.gok[2 * (size_t)p] : a.w_cw[p];
+        gcm_iv_rtp(salt, w2, roc, bswap(w0) & 0xffffu, gp.iv);
+    } else {
+        const uint32_t w1 = *reinterpret_cast<const uint32_t *>(pkt + 4); // SSRC
+        uint32_t word;
+        if (MODE == kGcmSeal) {
+            j = gcm_packet_job(1, 0, L, C, 0, 0u, 1);
+            if (j.status != kGcmNoStatus) return false;
+            word = (a.w_cw[p] & 0x7FFFFFFFu) | 0x80000000u; // always E = 1 (RFC 7714 9.1)
+        } else {
+            j = gcm_packet_job(1, 1, L, C, 0, 0u, 1); // where the word lies does not depend on E
+            if (j.status != kGcmNoStatus) return false;
+            word = ld_be32(pkt + j.word_at);
+            j = gcm_packet_job(1, 1, L, C, 0, 0u, (int)(word >> 31));
+            if (j.status != kGcmNoStatus) return false;
+            if (MODE == kGcmDecipher && !(word >> 31)) return false; // E = 0: nothing was ciphered
+        }
+        gcm_iv_rtcp(salt, w1, word, gp.iv);
+        gp.tail = bswap(word);
+        gp.tail_len = 4;
+    }
+    if (MODE == kGcmDecipher && !j.decipher) return false; // DISCARD / SILENCE
+    gp.aad_len = j.aad_len;
+    gp.len = j.data_len;
+    return true;
+}
+
+// The engine's passes (k_gcm's, to the byte and to the scratch word): wave w of
+// a workgroup takes packet 4 * blockIdx.x + w.  Whether it has work is decided
+// as in k_gcm -- packet index, final status, p_slot, the key set's mark -- and
+// is wave-uniform, as is the key set, so there is no key-set loop; a workgroup
+// none of whose packets has GCM work leaves before filling the image.  The
+// powers are read from the GcmPow table in place (16 B per lane, once per 64
+// blocks).  One lane writes the tag, the word and the scratch results.
+template <int MODE>
+__global__ __launch_bounds__(kGcmWaveBlock) void k_gcm_wave(BundleArgs a) {
+    __shared__ uint32_t s_te[kTeWords]; // the image stays at LDS 0
+    const uint32_t p = blockIdx.x * (uint32_t)(kGcmWaveBlock / 64) + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    bool todo = false;
+    uint32_t ks_id = 0u;
+    if (p < a.n && (MODE == kGcmVerify || a.status[p] == SRTP_STATUS_OK)) {
+        const uint32_t slot = a.p_slot[p];
+        if (slot != kNoSlot) {
+            ks_id = a.ctx[slot].ks;
+            todo = a.keysets[ks_id].pad == kGcmMark;
+        }
+    }
+    if (!__syncthreads_or(todo)) return;
+    fill_te4(s_te);
+    if (!todo) return;
+    const uint32_t ks_u = sgpr(ks_id);
+    GcmJob j;
+    GcmPkt gp;
+    uint8_t *pkt;
+    if (!gcm_prep<MODE>(a, ks_u, p, lane == 0u, j, gp, pkt)) return;
+    const GcmKeys *gk = a.gcmkeys + ks_u;
+    const uint32_t *pw = reinterpret_cast<const uint32_t *>(a.gcmpow[ks_u].pow);
+    RoundKeys256 rk;
+    load_rk256_uniform(gk->rk, rk);
+    const GcmBatchCipher cipher{reinterpret_cast<const char *>(s_te), te_base(), rk, sgpr((uint32_t)gk->nr) == 14u};
+    uint32_t tag[4];
+    if (MODE == kGcmDecipher) {
+        gcm_packet_wave<kGcmDecipher>(cipher, pw, gp, lane, tag);
+    } else if (MODE == kGcmSeal) {
+        gcm_packet_wave<kGcmSeal>(cipher, pw, gp, lane, tag);
+        if (lane == 0u) {
+            gcm_store(pkt + j.tag_at, 16, tag);
+            if (j.word_at >= 0) {
+                const uint32_t w[4] = {gp.tail, 0u, 0u, 0u};
+                gcm_store(pkt + j.word_at, 4, w);
+            }
+        }
+    } else {
+        uint32_t mask[4], got[4];
+        gcm_packet_wave<kGcmVerify>(cipher, pw, gp, lane, tag, mask);
+        if (lane == 0u) {
+            gcm_load(pkt + j.tag_at, 16, got);
+            uint32_t *S = a.mid + 5 * (size_t)p;
+            uint32_t diff = 0u;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                diff |= tag[k] ^ got[k];
+                S[k] = tag[k] ^ mask[k] ^ got[k];
+            }
+            a.gok[2 * (size_t)p + 1] = diff == 0u ? 1u : 0u;
+        }
+    }
+}
+
 // ============================================================== maintenance
 __global__ void k_remove_transformer(uint64_t *keys, CtxState *ctx, uint32_t cap, uint32_t tid) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -5337,7 +5679,21 @@ hipError_t launch_gcm_aead(const GcmBatch &g, hipStream_t s) {
     hipLaunchKernelGGL(k_gcm_aead, dim3((g.n + b - 1) / b), dim3(b), 0, s, g);
     return hipGetLastError();
 }
+hipError_t launch_gcm_aead_wave(const GcmBatchWave &g, hipStream_t s) {
+    const uint32_t per = (uint32_t)(kGcmWaveBlock / 64);
+    hipLaunchKernelGGL(k_gcm_aead_wave, dim3((g.b.n + per - 1) / per), dim3(kGcmWaveBlock), 0, s, g);
+    return hipGetLastError();
+}
 hipError_t launch_gcm(const BundleArgs &a, int mode, hipStream_t s) {
+    const bool wave = a.gcm_route ? a.gcm_route == kGcmRouteWave : a.n <= kGcmWaveMax;
+    if (wave) { // a wave per packet (the per-packet paths' small bundles)
+        const uint32_t per = (uint32_t)(kGcmWaveBlock / 64);
+        const dim3 grid((a.n + per - 1) / per), block(kGcmWaveBlock);
+        if (mode == kGcmVerify) hipLaunchKernelGGL(k_gcm_wave<kGcmVerify>, grid, block, 0, s, a);
+        else if (mode == kGcmDecipher) hipLaunchKernelGGL(k_gcm_wave<kGcmDecipher>, grid, block, 0, s, a);
+        else hipLaunchKernelGGL(k_gcm_wave<kGcmSeal>, grid, block, 0, s, a);
+        return hipGetLastError();
+    }
     const uint32_t b = aes_block(a.n, (uint32_t)kGcmBlock);
     const dim3 grid((a.n + b - 1) / b), block(b);
     if (mode == kGcmVerify) hipLaunchKernelGGL(k_gcm<kGcmVerify>, grid, block, 0, s, a);

@@ -88,6 +88,14 @@ struct alignas(256) GcmKeys {
     uint64_t htab[16][2]; // gcm_htable(E_K(0^128))
 };
 static_assert(sizeof(GcmKeys) == 512 && sizeof(GcmKeys) == sizeof(GcmKeyArg), "GcmKeys is 512 B");
+// The powers H^1 .. H^64 of a GCM key set's hash key (host_crypto.h
+// gcm_hpowers), indexed by key-set id in a table beside GcmKeys: pow[k] =
+// {low, high} halves of H^(k + 1), as htab's entries.  k_gcm_wave's lanes
+// multiply a block each by one of them.
+struct alignas(256) GcmPow {
+    uint64_t pow[64][2];
+};
+static_assert(sizeof(GcmPow) == 1024, "GcmPow is 1 KB");
 constexpr uint32_t kGcmMark = 0x47434d31u; // KeySet::pad of a GCM key set ("GCM1")
 
 struct FactoryRec {      // SRTPContextFactory

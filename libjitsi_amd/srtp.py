@@ -249,6 +249,13 @@ class SRTPEngine:
         on a new engine.  Existing GCM factories keep working when turned off."""
         N.check(N.lib().srtp_engine_enable_aead(self.h, int(bool(on))), self.h, "enable_aead")
 
+    @property
+    def trailer_room(self) -> int:
+        """srtp_engine_trailer_room: the room the per-packet paths leave for
+        protect's trailer -- 16, or 20 once enable_aead is on.  Aggregators and
+        RawPacket batches sample it when they are created."""
+        return int(N.lib().srtp_engine_trailer_room(self.h))
+
     def read_timing(self) -> dict:
         """{stage: (total ms, bundles)} since the last read (HIP events)."""
         ms = (C.c_double * len(N.STAGES))()
@@ -607,6 +614,9 @@ class SRTPAggregator:
             N.check(N.lib().srtp_aggregator_create(engine.h, C.byref(o), self._cb, None, C.byref(h)),
                     engine.h, "srtp_aggregator_create")
         self.h = h
+        # the room behind a protect packet, sampled from the engine at creation
+        # (srtp_aggregator_trailer_room): 16, or 20 with AES-GCM on
+        self.trailer_room = int(N.lib().srtp_aggregator_trailer_room(h))
 
     def submit(self, reverse: bool, transformer: "_SRTPBase", data: bytes, flags: int = 0,
                cookie: int = 0) -> int:
@@ -622,7 +632,7 @@ class SRTPAggregator:
         """Synchronous (srtp_aggregator_transform): (status, bytes) of one
         packet, sharing bundles with concurrent callers."""
         data = bytes(data)
-        cap = len(data) if reverse else len(data) + 16
+        cap = len(data) if reverse else len(data) + self.trailer_room
         out = (C.c_uint8 * max(cap, 1))()
         st, ol = C.c_int32(), C.c_uint32()
         N.check(N.lib().srtp_aggregator_transform(self.h, int(reverse), transformer.tid, data, len(data),
@@ -719,7 +729,9 @@ class RawPacket:
         return len(self.buffer) < self.offset + self.length or self.length < 12
 
 
-TRAILER_ROOM = 16  # largest trailer: SRTCP E|index (4) + 12-byte tag
+# largest trailer: SRTCP E|index (4) + 12-byte tag.  An engine with AES-GCM on
+# needs 20 (SRTPEngine.trailer_room; pack's ``room``)
+TRAILER_ROOM = 16
 
 
 def block_encrypt(enc_type: int, key: bytes, block: bytes) -> bytes:
@@ -771,8 +783,25 @@ def aes_gcm(key: bytes, iv: bytes, aad: bytes, data: bytes, tag: Optional[bytes]
     return (out, bytes(t)) if tag is None else out
 
 
+def gf128_mul(a: bytes, b: bytes) -> bytes:
+    """a * b in GF(2^128), 16-byte blocks in GCM's bit order (srtp_gf128_mul)."""
+    out = (C.c_uint8 * 16)()
+    assert len(a) == 16 and len(b) == 16
+    N.check(N.lib().srtp_gf128_mul(bytes(a), bytes(b), out), None, "gf128_mul")
+    return bytes(out)
+
+
+def gcm_hpowers(h: bytes):
+    """[h^1, ..., h^64] as 16-byte blocks (srtp_gcm_hpowers): the powers of the
+    hash key the wave-per-packet GCM kernels multiply by."""
+    out = (C.c_uint8 * 1024)()
+    assert len(h) == 16
+    N.check(N.lib().srtp_gcm_hpowers(bytes(h), out), None, "gcm_hpowers")
+    return [bytes(out[16 * k:16 * k + 16]) for k in range(64)]
+
+
 def aes_gcm_device(engine, key: bytes, seg, off, aad_len, length, iv, tag, result=None,
-                   open: bool = False, n: Optional[int] = None, stream=None) -> None:
+                   open: bool = False, n: Optional[int] = None, stream=None, wave: bool = False) -> None:
     """AES-GCM on the GPU for a batch of packets under one key
     (srtp_aes_gcm_device): the device twin of :func:`aes_gcm`.  All buffers are
     torch tensors on ``engine``'s GPU: packet i is ``seg[off[i] : off[i] +
@@ -781,7 +810,9 @@ def aes_gcm_device(engine, key: bytes, seg, off, aad_len, length, iv, tag, resul
     n x 16 bytes.  Seals in place and writes ``tag``; with ``open`` it checks
     ``tag`` instead: ``result[i]`` (int32) is 1 and the data untouched on a
     mismatch, else 0 and the data deciphered.  Async on ``stream`` like
-    :meth:`SRTPEngine.transform_device`; touches none of the engine's state."""
+    :meth:`SRTPEngine.transform_device`; touches none of the engine's state.
+    ``wave``: a wave per packet instead of a lane (srtp_aes_gcm_device_ex with
+    SRTP_GCM_BATCH_WAVE); the results are the same to the byte."""
     if n is None:
         n = off.numel()
     for t, size, what in ((off, 4, "off"), (aad_len, 4, "aad_len"), (length, 4, "length"),
@@ -795,9 +826,10 @@ def aes_gcm_device(engine, key: bytes, seg, off, aad_len, length, iv, tag, resul
     if open and result is None and n:
         raise ValueError("open needs a result tensor")
     sp = getattr(stream, "cuda_stream", stream)
-    rc = N.lib().srtp_aes_gcm_device(
+    rc = N.lib().srtp_aes_gcm_device_ex(
         engine.h, int(bool(open)), bytes(key), len(key), seg.data_ptr(), off.data_ptr(), aad_len.data_ptr(),
-        length.data_ptr(), iv.data_ptr(), tag.data_ptr(), None if result is None else result.data_ptr(), n, sp)
+        length.data_ptr(), iv.data_ptr(), tag.data_ptr(), None if result is None else result.data_ptr(), n,
+        N.GCM_BATCH_WAVE if wave else 0, sp)
     N.check(rc, engine.h, "srtp_aes_gcm_device")
 
 
@@ -822,7 +854,8 @@ def derive_session_keys(masterKey: bytes, masterSalt: bytes, rtcp: bool = False)
     return bytes(enc), bytes(auth), bytes(salt)
 
 
-def pack(pkts: Sequence[Optional[RawPacket]], predicate=None, reverse: bool = False):
+def pack(pkts: Sequence[Optional[RawPacket]], predicate=None, reverse: bool = False,
+         room: int = TRAILER_ROOM):
     """RawPacket[] -> (seg, off, len, cap, flags): the marshalling a JNI shim
     does.  Each packet region is 16-byte aligned and holds the
     packet's buffer bytes from its offset; ``cap`` is the Java buffer's length
@@ -832,7 +865,7 @@ def pack(pkts: Sequence[Optional[RawPacket]], predicate=None, reverse: bool = Fa
     form of RawPacket.append / grow), so a packet whose header-extension
     length field lies past its buffer reads the zero padding there instead of
     throwing (the one protect-side difference from the reference's
-    AIOOBE).  ``None`` elements and packets the predicate rejects are flagged
+    AIOOBE); ``room`` is that room, the engine's ``trailer_room``.  ``None`` elements and packets the predicate rejects are flagged
     SKIP (SinglePacketTransformer.java:121-216 never hands them to the
     transformer)."""
     n = len(pkts)
@@ -848,7 +881,7 @@ def pack(pkts: Sequence[Optional[RawPacket]], predicate=None, reverse: bool = Fa
         else:
             avail = len(p.buffer) - p.offset
             fits = p.length <= avail
-            cap[i] = max(avail, p.length + TRAILER_ROOM) if fits and not reverse else max(avail, 0)
+            cap[i] = max(avail, p.length + room) if fits and not reverse else max(avail, 0)
             length[i] = p.length
             flags[i] = p.flags & (N.PKT_FLAG_DISCARD | N.PKT_FLAG_SILENCE)
         off[i] = pos
@@ -924,7 +957,7 @@ def _packet_aggregator(engine) -> "SRTPAggregator":
 
 
 _grow_tls = threading.local()
-_GROW = 65536 + 16
+_GROW = 65536 + 20
 
 
 def _rawpacket_one(engine, reverse: bool, tid: int, pkt: "RawPacket"):

@@ -54,6 +54,12 @@ JNIEXPORT void JNICALL JFN(dispatchDestroy)(JNIEnv *env, jclass c, jlong d) {
     srtp_dispatch_destroy((srtp_dispatch *)H(d));
 }
 
+/* The AES-GCM switch of every shard's engine; before aggregatorCreate and the
+ * first transformPackets, which sample the trailer room it decides. */
+JNIEXPORT jint JNICALL JFN(dispatchEnableAead)(JNIEnv *env, jclass c, jlong d, jboolean on) {
+    return srtp_dispatch_enable_aead((srtp_dispatch *)H(d), on ? 1 : 0);
+}
+
 /* SRTPContextFactory(sender, masterKey, masterSalt, srtpPolicy, srtcpPolicy):
  * policies as int[6] {encType, encKeyLength, authType, authKeyLength,
  * authTagLength, saltKeyLength} (SRTPPolicy.java:107-120). */
@@ -297,7 +303,7 @@ JNIEXPORT void JNICALL JFN(aggregatorDestroy)(JNIEnv *env, jclass c, jlong a) {
 
 /* Per-thread native copies of one packet: its bytes from the offset on, and
  * the result where the reference reallocates. */
-#define ONE_BYTES (65535 + 16)
+#define ONE_BYTES (65535 + 20) /* a region of at most 65535 bytes; 20: the largest trailer room */
 static __thread uint8_t *tl_pkt, *tl_grow;
 
 /* Reads a RawPacket's fields and copies its bytes from the offset on (at

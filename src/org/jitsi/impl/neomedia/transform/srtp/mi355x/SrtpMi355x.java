@@ -37,6 +37,16 @@ public final class SrtpMi355x
     public static final String LANE_MB_PNAME = "org.jitsi.impl.neomedia.transform.srtp.mi355x.LANE_MB";
     public static final String LANE_SLOTS_PNAME = "org.jitsi.impl.neomedia.transform.srtp.mi355x.LANE_SLOTS";
 
+    /**
+     * The AES-GCM switch (RFC 7714: AEAD_AES_128_GCM / AEAD_AES_256_GCM,
+     * srtp_dispatch_enable_aead), off unless this property is true.  It is
+     * turned on right after the dispatcher is created, so before the
+     * aggregator and every thread's RawPacket staging exist: those sample
+     * their trailer room (20 bytes instead of 16, what GCM SRTCP appends)
+     * when they are created.
+     */
+    public static final String AEAD_PNAME = "org.jitsi.impl.neomedia.transform.srtp.mi355x.AEAD";
+
     /** One dispatcher per process: every GPU of the node, SSRC-sharded. */
     private static long dispatch;
 
@@ -53,13 +63,14 @@ public final class SrtpMi355x
         {
             // SRTPCryptoContext.readConfigurationServicePropertiesOnce
             // (SRTPCryptoContext.java:105-121): the same property, the same default
-            boolean checkReplay = true;
+            boolean checkReplay = true, aead = false;
             int n = deviceCount();
             ConfigurationService cfg = LibJitsi.getConfigurationService();
             if (cfg != null)
             {
                 checkReplay = cfg.getBoolean(SRTPCryptoContext.CHECK_REPLAY_PNAME, checkReplay);
                 n = cfg.getInt(GPUS_PNAME, n);
+                aead = cfg.getBoolean(AEAD_PNAME, aead);
             }
             if (n < 1)
                 throw new IllegalStateException("srtp_mi355x: no GPU");
@@ -69,6 +80,8 @@ public final class SrtpMi355x
             dispatch = dispatchCreate(devices, checkReplay, 0);
             if (dispatch == 0)
                 throw new IllegalStateException("srtp_mi355x: no engine");
+            if (aead)
+                check(dispatchEnableAead(dispatch, true));
         }
         return dispatch;
     }
@@ -109,6 +122,8 @@ public final class SrtpMi355x
     static native int deviceCount();
     static native long dispatchCreate(int[] devices, boolean checkReplay, int maxContexts);
     static native void dispatchDestroy(long d);
+    /** srtp_dispatch_enable_aead: before aggregatorCreate (see AEAD_PNAME). */
+    static native int dispatchEnableAead(long d, boolean on);
     static native int factoryCreate(long d, boolean sender, byte[] key, byte[] salt, int[] srtpPolicy,
                                     int[] srtcpPolicy);
     static native int factoryClose(long d, int factory);
