@@ -240,6 +240,8 @@ typedef struct {
                                             transformer (tid < 0) that srtp_aggregator_* seals
                                             unclaimed; not in status[SRTP_STATUS_SKIPPED] */
     uint64_t small_bundles;              /* bundles run by k_small: every phase in one launch */
+    uint64_t small_aead_bundles;         /* ... by its GCM instance (an engine that holds an
+                                            AES-GCM key set); not in small_bundles */
 } srtp_stats;
 int srtp_engine_stats(srtp_engine *e, srtp_stats *out);
 
@@ -269,12 +271,27 @@ int srtp_engine_stats(srtp_engine *e, srtp_stats *out);
 #define SRTP_DEBUG_NO_GCM_WAVE 0x10u
 #define SRTP_DEBUG_FORCE_GCM_WAVE 0x20u
 int32_t srtp_gcm_wave_max(void);
+/* An engine that holds an AES-GCM key set runs a bundle of up to
+ * srtp_small_aead_max() packets in one launch (k_small's GCM instance,
+ * srtp_stats.small_aead_bundles), larger ones on the multi-kernel path: the
+ * instance checks the GCM tags before the walk in one workgroup, a wave per
+ * packet, and loses to the chain once a wave has more than one.
+ * SRTP_DEBUG_FORCE_SMALL lifts the limit to k_small's own 255 packets (so that
+ * every parity case reaches the instance's several workgroups; A/B
+ * measurements); NO_SMALL, the WIDE hooks and the GCM_WAVE hooks keep every
+ * bundle off it.  Results must not change. */
+#define SRTP_DEBUG_FORCE_SMALL 0x40u
+int32_t srtp_small_aead_max(void);
 int srtp_engine_set_debug(srtp_engine *e, uint32_t flags);
 /* The AES-GCM switch (RFC 7714 profiles, see SRTP_AESGCM_ENCRYPTION): off on a
  * new engine.  While on, srtp_factory_create accepts the GCM policy shape for
  * its SRTP and / or SRTCP policy; turning it off again refuses new such
  * factories and leaves existing ones working.  An engine that holds a GCM
- * factory runs every bundle on the multi-kernel path. */
+ * factory still runs its bundles of up to srtp_small_aead_max() packets -- the
+ * per-packet callers' lone calls among them, direct mode included -- in one
+ * launch (k_small's GCM instance, srtp_stats.small_aead_bundles), as long as
+ * its other key sets are AES-CM / NULL cipher + HMAC-SHA1 ones; its larger
+ * bundles run on the multi-kernel path (no split path). */
 int srtp_engine_enable_aead(srtp_engine *e, int32_t on);
 /* The room, in bytes, that the per-packet paths leave behind a packet for
  * protect's trailer: 16 (SRTCP's E|index word and a 12-byte tag), or 20 when

@@ -33,6 +33,7 @@ DEBUG_NO_WIDE = 0x4     # every bundle on the fused kernels
 DEBUG_NO_SMALL = 0x8    # bundles of up to 255 packets off k_small (one launch per bundle)
 DEBUG_NO_GCM_WAVE = 0x10     # the AES-GCM passes always a lane per packet (k_gcm)
 DEBUG_FORCE_GCM_WAVE = 0x20  # ... always a wave per packet (k_gcm_wave)
+DEBUG_FORCE_SMALL = 0x40     # k_small's GCM instance up to 255 packets, past srtp_small_aead_max()
 GCM_BATCH_WAVE = 0x1         # srtp_aes_gcm_device_ex: a wave per packet
 ABI_VERSION = 3
 AGG_SEAL_IDLE = 0x1
@@ -79,6 +80,7 @@ EXPORTED = [
     "srtp_engine_enable_aead", "srtp_gcm_packet_job", "srtp_dtls_profile_keys_ex",
     "srtp_dispatch_enable_aead",
     "srtp_aes_gcm_device_ex", "srtp_gf128_mul", "srtp_gcm_hpowers", "srtp_gcm_wave_max",
+    "srtp_small_aead_max",
     "srtp_trailer_room", "srtp_engine_trailer_room", "srtp_aggregator_trailer_room",
 ]
 STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
@@ -128,7 +130,7 @@ class Stats(C.Structure):
                  ("status", C.c_uint64 * NUM_STATUS)] +
                 [(n, C.c_uint64) for n in ("roc_rechecks", "repaired", "ctx_overflow", "ctx_live",
                                            "ctx_tombstones", "ctx_slots", "rehashes", "chain_stalls", "long_walked",
-                                           "holes", "small_bundles")])
+                                           "holes", "small_bundles", "small_aead_bundles")])
 
     def as_dict(self) -> dict:
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "status"}
@@ -283,6 +285,8 @@ def lib() -> C.CDLL:
     L.srtp_gcm_hpowers.argtypes = [C.c_char_p, pu8]
     L.srtp_gcm_wave_max.argtypes = []
     L.srtp_gcm_wave_max.restype = i32
+    L.srtp_small_aead_max.argtypes = []
+    L.srtp_small_aead_max.restype = i32
     L.srtp_trailer_room.argtypes = [i32]
     L.srtp_trailer_room.restype = i32
     L.srtp_engine_trailer_room.argtypes = [vp]

@@ -41,6 +41,7 @@ struct srtp_engine {
     uint32_t n_gcm = 0;           // AES-GCM key sets created: k_gcm and the walk's GCM instances only when > 0
     bool aead = false;            // srtp_engine_enable_aead: new factories may carry the GCM policy
     uint32_t n_not_wide = 0;      // key sets the split path cannot run (not AES-CM / NULL cipher + HMAC-SHA1)
+    uint32_t n_not_small = 0;     // those of them that are not AES-GCM either: k_small cannot run them
     uint32_t n_keysets = 0, max_keysets = 0;
     FactoryRec *d_factories = nullptr;
     std::vector<FactoryRec> factories;
@@ -94,7 +95,7 @@ struct srtp_engine {
 #ifdef SRTP_STAMPS
     unsigned long long *d_stamps[2] = {nullptr, nullptr}; // diagnostic build: protect / unprotect
 #endif
-    uint64_t n_bundles = 0, n_packets = 0, n_rehash = 0, n_small = 0;
+    uint64_t n_bundles = 0, n_packets = 0, n_rehash = 0, n_small = 0, n_small_aead = 0;
     uint32_t serial = 1;
 
     // staging for srtp_transform_host
@@ -684,6 +685,11 @@ int srtp_factory_create(srtp_engine *e, int32_t sender, const uint8_t *mk, int32
         e->n_not_wide += (k.ext || k.pad == kGcmMark || k.auth_type != SRTP_HMACSHA1_AUTHENTICATION ||
                           (k.enc_type != SRTP_AESCM_ENCRYPTION && k.enc_type != SRTP_NULL_ENCRYPTION))
                              ? 1u : 0u;
+    for (const KeySet &k : ks)
+        e->n_not_small += (k.pad != kGcmMark &&
+                           (k.ext || k.auth_type != SRTP_HMACSHA1_AUTHENTICATION ||
+                            (k.enc_type != SRTP_AESCM_ENCRYPTION && k.enc_type != SRTP_NULL_ENCRYPTION)))
+                              ? 1u : 0u;
     memset(ks, 0, sizeof ks);
     memset(f8, 0, sizeof f8);
     FactoryRec f;
@@ -782,13 +788,16 @@ int srtp_transformer_close(srtp_engine *e, int32_t t) {
     return SRTP_OK;
 }
 
-// A bundle of up to kSmallMaxN packets under the split path's key-set rule
-// runs every phase in one launch (k_small), unless a debug hook needs the
-// multi-kernel chain.
+// A bundle of up to kSmallMaxN packets of an engine whose key sets are all the
+// split path's or AES-GCM ones runs every phase in one launch (k_small; once the
+// engine holds a GCM key set its GCM instance, up to kSmallGcmMax packets),
+// unless a debug hook needs the multi-kernel chain (the GCM route hooks:
+// k_gcm_wave / k_gcm).
 static bool small_path(const srtp_engine *e, uint32_t n) {
-    const bool wide_ok = e->n_not_wide == 0 && !(e->dbg & SRTP_DEBUG_NO_WIDE);
-    return wide_ok && n <= kSmallMaxN && !(e->dbg & SRTP_DEBUG_FORCE_CHAIN_STALL) &&
-           !(e->dbg & (SRTP_DEBUG_FORCE_WIDE | SRTP_DEBUG_NO_SMALL));
+    const uint32_t lim = e->n_gcm && !(e->dbg & SRTP_DEBUG_FORCE_SMALL) ? kSmallGcmMax : kSmallMaxN;
+    return e->n_not_small == 0 && n <= lim &&
+           !(e->dbg & (SRTP_DEBUG_FORCE_CHAIN_STALL | SRTP_DEBUG_NO_WIDE | SRTP_DEBUG_FORCE_WIDE | SRTP_DEBUG_NO_SMALL |
+                       SRTP_DEBUG_NO_GCM_WAVE | SRTP_DEBUG_FORCE_GCM_WAVE));
 }
 
 // abort: SinglePacketTransformer's abort-on-throw for this bundle (-1: the
@@ -902,7 +911,8 @@ static int transform_locked(srtp_engine *e, int32_t reverse, const int32_t *tids
         e->ctl_clean[c ^ 1] = true;
         if (a.abort_on_error) e->emin_filled[c ^ 1] = a.n_transformers;
         e->ctl_cur = c ^ 1;
-        e->n_small++;
+        if (e->n_gcm) e->n_small_aead++;
+        else e->n_small++;
     } else {
     // a one-tile bundle is sorted by one workgroup in one launch
     const bool one_tile = n <= sort_tile_records();
@@ -1270,6 +1280,7 @@ int srtp_engine_stats(srtp_engine *e, srtp_stats *out) {
     out->long_walked = sum[kCtrLongWalked];
     out->holes = sum[kCtrStatus + kStatusHole];
     out->small_bundles = e->n_small;
+    out->small_aead_bundles = e->n_small_aead;
     return SRTP_OK;
 }
 
@@ -1280,7 +1291,7 @@ int32_t srtp_device_count(void) {
 
 int srtp_engine_set_debug(srtp_engine *e, uint32_t flags) {
     if (!e || (flags & ~(SRTP_DEBUG_FORCE_CHAIN_STALL | SRTP_DEBUG_FORCE_WIDE | SRTP_DEBUG_NO_WIDE | SRTP_DEBUG_NO_SMALL |
-                        SRTP_DEBUG_NO_GCM_WAVE | SRTP_DEBUG_FORCE_GCM_WAVE)))
+                        SRTP_DEBUG_NO_GCM_WAVE | SRTP_DEBUG_FORCE_GCM_WAVE | SRTP_DEBUG_FORCE_SMALL)))
         return SRTP_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     e->dbg = flags;
@@ -1440,6 +1451,7 @@ int srtp_gcm_hpowers(const uint8_t h[16], uint8_t out[1024]) {
 }
 
 int32_t srtp_gcm_wave_max(void) { return (int32_t)kGcmWaveMax; }
+int32_t srtp_small_aead_max(void) { return (int32_t)kSmallGcmMax; }
 
 int32_t srtp_trailer_room(int32_t aead) { return (int32_t)trailer_room(aead); }
 

@@ -166,6 +166,15 @@ hipError_t launch_mac_wide(const BundleArgs &a, hipStream_t s);
 // or NULL cipher with HMAC-SHA1): parse, sort, (tag check,)
 // walk, keystream and (MAC, trailer) in one workgroup and one launch (k_small).
 constexpr uint32_t kSmallMaxN = 255u;
+// An engine that holds AES-GCM key sets launches k_small's GCM instance, for
+// bundles of up to kSmallGcmMax packets: workgroup 0's eight waves verify the
+// bundle's GCM tags before the walk, a wave per packet, and from two packets
+// per wave on the chain's k_gcm_wave (every packet's wave at once) is faster.
+// The largest size of profiles/gcm_small/sweep.json at which the one-launch
+// route's median lies below the chain's by more than the chain's spread, both
+// ways, for GCM and for AES-CM + HMAC bundles.  SRTP_DEBUG_FORCE_SMALL: up to
+// kSmallMaxN.
+constexpr uint32_t kSmallGcmMax = 8u;
 hipError_t launch_small(const BundleArgs &a, hipStream_t s);
 // Packet regions [doff[j], + cap[j] rounded to 16) of a device segment from /
 // to [src[j], ...) of device-mapped host memory (a dispatcher shard's gather of

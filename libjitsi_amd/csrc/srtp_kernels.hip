@@ -35,6 +35,12 @@
 //              HMAC-SHA1 (one read and one write of the packet bytes).
 //   k_unprotect_fix [unprotect] statuses/lengths out; undoes/redoes the rare
 //              packets whose speculation the walk overturned.
+//   k_small    [bundles of up to kSmallMaxN packets of engines whose key sets are
+//              AES-CM / NULL cipher + HMAC-SHA1 ones] the whole pipeline in one
+//              launch, its phases behind barriers.  k_small<REV, true>: its GCM
+//              instance, which engines that also hold AES-GCM key sets launch
+//              for bundles of up to kSmallGcmMax packets -- a GCM packet takes
+//              k_gcm_wave's passes (gcm_wave_pass) in place of the HMAC steps.
 //
 // Outside the bundle pipeline:
 //   k_gcm_aead [srtp_aes_gcm_device] AES-GCM of a batch of packets under one
@@ -5469,20 +5475,14 @@ __device__ __forceinline__ bool gcm_prep(const BundleArgs &a, uint32_t ks_u, uin
     return true;
 }
 
-// The engine's passes (k_gcm's, to the byte and to the scratch word): wave w of
-// a workgroup takes packet 4 * blockIdx.x + w.  Whether it has work is decided
-// as in k_gcm -- packet index, final status, p_slot, the key set's mark -- and
-// is wave-uniform, as is the key set, so there is no key-set loop; a workgroup
-// none of whose packets has GCM work leaves before filling the image.  The
-// powers are read from the GcmPow table in place (16 B per lane, once per 64
-// blocks).  One lane writes the tag, the word and the scratch results.
+// Whether the calling wave has pass MODE's work on packet p, decided as in
+// k_gcm -- packet index, final status (the passes after the walk), p_slot, the
+// key set's mark -- before any packet pointer or table index is formed; ks_id:
+// the packet's key set.  Wave-uniform when p is.
 template <int MODE>
-__global__ __launch_bounds__(kGcmWaveBlock) void k_gcm_wave(BundleArgs a) {
-    __shared__ uint32_t s_te[kTeWords]; // the image stays at LDS 0
-    const uint32_t p = blockIdx.x * (uint32_t)(kGcmWaveBlock / 64) + (threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63u;
+__device__ __forceinline__ bool gcm_wave_todo(const BundleArgs &a, uint32_t p, uint32_t &ks_id) {
     bool todo = false;
-    uint32_t ks_id = 0u;
+    ks_id = 0u;
     if (p < a.n && (MODE == kGcmVerify || a.status[p] == SRTP_STATUS_OK)) {
         const uint32_t slot = a.p_slot[p];
         if (slot != kNoSlot) {
@@ -5490,9 +5490,18 @@ __global__ __launch_bounds__(kGcmWaveBlock) void k_gcm_wave(BundleArgs a) {
             todo = a.keysets[ks_id].pad == kGcmMark;
         }
     }
-    if (!__syncthreads_or(todo)) return;
-    fill_te4(s_te);
-    if (!todo) return;
+    return todo;
+}
+
+// Pass MODE on packet p (gcm_wave_todo said so) by the calling wave, the
+// T-table image s_te at LDS 0: k_gcm's results, to the byte and to the scratch
+// word.  The powers are read from the GcmPow table in place (16 B per lane,
+// once per 64 blocks).  One lane writes the tag, the word and the scratch
+// results.  Every early end is a return from here, not from the kernel
+// (k_small's barriers follow its calls).
+template <int MODE>
+__device__ __forceinline__ void gcm_wave_pass(const BundleArgs &a, const uint32_t *s_te, uint32_t p, uint32_t ks_id,
+                                              uint32_t lane) {
     const uint32_t ks_u = sgpr(ks_id);
     GcmJob j;
     GcmPkt gp;
@@ -5530,6 +5539,23 @@ __global__ __launch_bounds__(kGcmWaveBlock) void k_gcm_wave(BundleArgs a) {
             a.gok[2 * (size_t)p + 1] = diff == 0u ? 1u : 0u;
         }
     }
+}
+
+// The engine's passes: wave w of a workgroup takes packet 4 * blockIdx.x + w.
+// Whether it has work is wave-uniform, as is the key set, so there is no
+// key-set loop; a workgroup none of whose packets has GCM work leaves before
+// filling the image.
+template <int MODE>
+__global__ __launch_bounds__(kGcmWaveBlock) void k_gcm_wave(BundleArgs a) {
+    __shared__ uint32_t s_te[kTeWords]; // the image stays at LDS 0
+    const uint32_t p = blockIdx.x * (uint32_t)(kGcmWaveBlock / 64) + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t ks_id;
+    const bool todo = gcm_wave_todo<MODE>(a, p, ks_id);
+    if (!__syncthreads_or(todo)) return;
+    fill_te4(s_te);
+    if (!todo) return;
+    gcm_wave_pass<MODE>(a, s_te, p, ks_id, lane);
 }
 
 // ============================================================== maintenance
@@ -6502,7 +6528,60 @@ __device__ __forceinline__ void small_push(const BundleArgs &a, uint32_t g, uint
     }
 }
 
-template <bool REV>
+// The GCM instance (engines that hold AES-GCM key sets; the others launch the
+// instances they always did): a packet whose key set carries kGcmMark takes
+// k_gcm_wave's passes, a wave per packet, in place of the HMAC steps -- before
+// the walk what k_unprotect leaves for it (gcm_guess) and the verify pass,
+// after the final statuses the decipher or the seal pass -- and every other
+// packet exactly the steps above.  A pass that ends early on a packet ends
+// inside gcm_wave_pass: every wave reaches every barrier.
+
+// Packet p has a context with a GCM key set.
+__device__ __forceinline__ bool small_is_gcm(const BundleArgs &a, uint32_t p) {
+    const uint32_t slot = a.p_slot[p];
+    return slot != kNoSlot && a.keysets[a.ctx[slot].ks].pad == kGcmMark;
+}
+
+// Unprotect, GCM packet p before the walk, what k_unprotect leaves for it:
+// mac_check's prologue, the ROC guess in gok[2p], and spec[p] without kSpecAes /
+// kSpecDid (unprotect_one on a NULL / NULL key set of tag length 0).
+__device__ __forceinline__ void gcm_guess(const BundleArgs &a, uint32_t p) {
+    const uint32_t slot = a.p_slot[p];
+    const uint32_t pos = a.spos[p];
+    CtxState st = a.ctx[slot];
+    const bool lng = pos >= kLongRank && a.sk_out[pos - kLongRank] == slot;
+    if (lng) {
+        const uint32_t hh = chain_head(a.sk_out, pos - kLongRank, slot);
+        const int32_t seq_h = (int32_t)(a.sv_out[hh].word & 0xffffu);
+        const int32_t seq = (int32_t)(a.sv_out[pos].word & 0xffffu);
+        const int64_t e = (int64_t)guess_roc(st, seq_h) * 65536 + seq_h + (int64_t)(pos - hh);
+        st.a = (int32_t)((e - seq + 32768) >> 16);
+        st.flags &= ~1u;
+    }
+    const KeySet *ks = a.keysets + st.ks;
+    if (ks->kind != SRTP_KIND_RTP) { // (L - 4 < 0: the walk throws; spec is 0 either way)
+        a.spec[p] = 0u;
+        return;
+    }
+    const uint32_t w0 = *reinterpret_cast<const uint32_t *>(a.seg + a.off[p]);
+    a.gok[2 * (size_t)p] = (uint32_t)guess_roc(st, (int32_t)(bswap(w0) & 0xffffu));
+    a.spec[p] = kSpecRtp | (a.flags && (a.flags[p] & (SRTP_PKT_FLAG_DISCARD | SRTP_PKT_FLAG_SILENCE)) ? kSpecSkip : 0u);
+}
+
+// Pass MODE over packets first, first + stride, ... (count of them), each by
+// one of the workgroup's waves in turn.
+template <int MODE>
+__device__ __forceinline__ void small_gcm_pass(const BundleArgs &a, const uint32_t *s_te, uint32_t first,
+                                               uint32_t stride, uint32_t count) {
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t i = sgpr(threadIdx.x >> 6); i < count; i += (uint32_t)(kSmallBlock / 64)) {
+        const uint32_t p = first + stride * i;
+        uint32_t ks_id;
+        if (gcm_wave_todo<MODE>(a, p, ks_id)) gcm_wave_pass<MODE>(a, s_te, p, ks_id, lane);
+    }
+}
+
+template <bool REV, bool GCM = false>
 __global__ __launch_bounds__(kSmallBlock) void k_small(BundleArgs a) {
     __shared__ uint32_t s[kSmallOffR + kSmallRWords];
     if (a.pk_host && blockIdx.x == 0) {
@@ -6514,9 +6593,10 @@ __global__ __launch_bounds__(kSmallBlock) void k_small(BundleArgs a) {
     const uint32_t t = threadIdx.x, n = a.n, g = blockIdx.x, G = gridDim.x;
     const uint32_t wv = t >> 6;
     const bool wave_mac = n <= kSmallWaveMacN; // (then G == 1)
+    bool late_fill = REV && wave_mac;
     if (t < kTeCounters) s_cnt[t] = 0u;
     // the T-table image now, unless it first holds an unprotect's wave MACs
-    if (!REV || !wave_mac) fill_te4(s); // ends with a barrier
+    if (!late_fill) fill_te4(s); // ends with a barrier
     if (g == 0) {
         // the next bundle's control block and abort limits (as k_parse)
         if (t == 0) *a.ctl_next = BundleCtl{};
@@ -6543,7 +6623,26 @@ __global__ __launch_bounds__(kSmallBlock) void k_small(BundleArgs a) {
         }
         __syncthreads();
         // 3. unprotect: the tag checks before the walk
-        if (REV) {
+        if (REV && GCM) {
+            // a GCM packet: the ROC guess, then the verify pass a wave per
+            // packet, which needs the image -- so a bundle of wave-MAC size
+            // that holds one fills it now and MACs its other packets a lane
+            // each (workgroup-uniform)
+            const bool gcm = t < n && small_is_gcm(a, t);
+            if (late_fill && __syncthreads_or(gcm)) {
+                late_fill = false;
+                fill_te4(s); // ends with a barrier
+            }
+            if (late_fill) {
+                if (wv < n) mac_check<true>(a, wv, s + wv * kWaveMacWords);
+            } else if (t < n) {
+                if (gcm) gcm_guess(a, t);
+                else mac_check<false>(a, t, nullptr);
+            }
+            __syncthreads(); // the guesses, before the waves read them
+            small_gcm_pass<kGcmVerify>(a, s, 0u, 1u, n);
+            __syncthreads();
+        } else if (REV) {
             if (wave_mac) {
                 if (wv < n) mac_check<true>(a, wv, s + wv * kWaveMacWords);
             } else if (t < n) {
@@ -6555,10 +6654,10 @@ __global__ __launch_bounds__(kSmallBlock) void k_small(BundleArgs a) {
         // pass, then the limit pass (k_walk's two launches)
         if (t < 64) {
             WalkShared<REV> &sh = *reinterpret_cast<WalkShared<REV> *>(r);
-            walk_tile<REV, false, 0>(a, sh, 0u, 1u);
+            walk_tile<REV, false, 0, GCM>(a, sh, 0u, 1u);
             if (a.abort_on_error && a.ctl->any_throw) {
                 walk_sync();
-                walk_tile<REV, false, 1>(a, sh, 0u, 1u);
+                walk_tile<REV, false, 1, GCM>(a, sh, 0u, 1u);
             }
         }
         __syncthreads();
@@ -6573,7 +6672,7 @@ __global__ __launch_bounds__(kSmallBlock) void k_small(BundleArgs a) {
                 __builtin_amdgcn_s_sleep(2);
         __syncthreads();
     }
-    if (REV && wave_mac) fill_te4(s); // ends with a barrier
+    if (late_fill) fill_te4(s); // ends with a barrier
     // 5. this workgroup's packets p = g + G * i: keystream jobs and their pair
     // counts, then the pairs' prefix
     const uint32_t m = n > g ? (n - g + G - 1u) / G : 0u;
@@ -6629,6 +6728,9 @@ __global__ __launch_bounds__(kSmallBlock) void k_small(BundleArgs a) {
             if (start + 16 * (j + 1) < end) xor_ks16(pkt + start + 16 * (j + 1), end - (start + 16 * (j + 1)), y);
         }
     }
+    // unprotect: the accepted GCM packets deciphered (their final statuses are
+    // wide_job_rev's, behind step 5's barrier)
+    if (REV && GCM) small_gcm_pass<kGcmDecipher>(a, s, g, G, m);
     __syncthreads();
     // 7. protect: final statuses, then the MAC over the ciphertext and the
     // trailer (the T-table image is free again for the wave MACs)
@@ -6643,7 +6745,18 @@ __global__ __launch_bounds__(kSmallBlock) void k_small(BundleArgs a) {
     if (!REV && t < m) s_fs[t] = (uint32_t)fs;
     __syncthreads();
     flush_status_counts(a, s_cnt);
-    if (!REV) {
+    if (!REV && GCM) {
+        // a GCM packet is sealed by a wave instead of MACed; the wave MACs'
+        // schedules would overwrite the image under it, so they run only in a
+        // workgroup without one (workgroup-uniform)
+        const bool gcm = fs == SRTP_STATUS_OK && small_is_gcm(a, p);
+        if (wave_mac && !__syncthreads_or(gcm)) {
+            if (wv < m && (int32_t)s_fs[wv] == SRTP_STATUS_OK) mac_seal<true>(a, wv, s + wv * kWaveMacWords);
+        } else if (fs == SRTP_STATUS_OK && !gcm) {
+            mac_seal<false>(a, p, nullptr);
+        }
+        small_gcm_pass<kGcmSeal>(a, s, g, G, m); // the tag and SRTCP's E|index word
+    } else if (!REV) {
         if (wave_mac) {
             if (wv < m && (int32_t)s_fs[wv] == SRTP_STATUS_OK) mac_seal<true>(a, wv, s + wv * kWaveMacWords);
         } else if (fs == SRTP_STATUS_OK) {
@@ -6660,8 +6773,14 @@ hipError_t launch_small(const BundleArgs &a, hipStream_t s) {
     if (a.n == 0) return hipSuccess;
     if (a.n > kSmallMaxN) return hipErrorInvalidValue;
     const dim3 grid((a.n + kSmallPerWg - 1u) / kSmallPerWg); // at most 16
-    if (a.reverse) hipLaunchKernelGGL(k_small<true>, grid, dim3(kSmallBlock), 0, s, a);
-    else hipLaunchKernelGGL(k_small<false>, grid, dim3(kSmallBlock), 0, s, a);
+    if (a.has_gcm) { // engines with AES-GCM key sets: instances of their own
+        if (a.reverse) hipLaunchKernelGGL((k_small<true, true>), grid, dim3(kSmallBlock), 0, s, a);
+        else hipLaunchKernelGGL((k_small<false, true>), grid, dim3(kSmallBlock), 0, s, a);
+    } else if (a.reverse) {
+        hipLaunchKernelGGL(k_small<true>, grid, dim3(kSmallBlock), 0, s, a);
+    } else {
+        hipLaunchKernelGGL(k_small<false>, grid, dim3(kSmallBlock), 0, s, a);
+    }
     return hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Small AES-GCM bundles on one MI355X: where a wave per packet (k_gcm_wave)
-beats a lane per packet (k_gcm), and what a lone per-packet call costs.
+beats a lane per packet (k_gcm), where one launch (k_small's GCM instance)
+beats the multi-kernel chain, and what a lone per-packet call costs.
 
 sweep   protect and unprotect of n 1200-byte GCM-128 SRTP packets (n distinct
         streams) through srtp_transform_device, each call between two HIP
@@ -11,6 +12,14 @@ sweep   protect and unprotect of n 1200-byte GCM-128 SRTP packets (n distinct
         when its median is below the lane route's by more than the lane
         route's spread, in both directions: kGcmWaveMax (srtp_kernels.h) is
         the largest such n.
+small   the same sweep with the one-launch route (SRTP_DEBUG_FORCE_SMALL: at
+        every size up to k_small's 255) against the chain (SRTP_DEBUG_NO_SMALL)
+        on an engine that holds a GCM factory, for GCM-128 SRTP bundles and
+        for AES_CM_128_HMAC_SHA1_80 bundles (--profile gcm,aescm).  The
+        one-launch route `wins` at n when its median is below the chain's by
+        more than the chain's spread, in both directions: kSmallGcmMax
+        (srtp_kernels.h) is the largest n up to which it wins for both
+        profiles.
 lone    the per-packet drop-in: p50 / p90 wall time of --calls synchronous
         srtp_aggregator_transform calls from one thread, for a 1200-byte GCM
         SRTP packet, a 200-byte GCM SRTCP packet and the 1200-byte
@@ -20,7 +29,7 @@ lone    the per-packet drop-in: p50 / p90 wall time of --calls synchronous
 once    one small GCM bundle each way and nothing else (the workload for
         rocprofv3 --kernel-trace --stats -- python tools/gcm_small_bench.py once).
 
-    python tools/gcm_small_bench.py sweep|lone|once [--out file.json] [--route default|lane|wave]
+    python tools/gcm_small_bench.py sweep|small|lone|once [--out file.json] [--route default|lane|wave|nosmall]
 """
 from __future__ import annotations
 
@@ -41,7 +50,9 @@ from libjitsi_amd import (SRTCPTransformer, SRTPAggregator, SRTPContextFactory, 
 from libjitsi_amd import _native as N  # noqa: E402
 
 PKT = 1200
-ROUTES = {"default": 0, "lane": getattr(N, "DEBUG_NO_GCM_WAVE", None), "wave": getattr(N, "DEBUG_FORCE_GCM_WAVE", None)}
+ROUTES = {"default": 0, "lane": getattr(N, "DEBUG_NO_GCM_WAVE", None), "wave": getattr(N, "DEBUG_FORCE_GCM_WAVE", None),
+          "small": getattr(N, "DEBUG_FORCE_SMALL", None), "chain": getattr(N, "DEBUG_NO_SMALL", None),
+          "nosmall": getattr(N, "DEBUG_NO_SMALL", None)}
 
 
 def pct(v, q):
@@ -60,15 +71,21 @@ def gcm_engine(n):
     return eng
 
 
-def sweep(args):
+def sweep(args, old="lane", new="wave", profile="gcm"):
+    """`new` against `old` (two of ROUTES), interleaved call by call on one engine."""
     import torch
     d = torch.device("cuda", 0)
     rows = []
-    pols = profile_policies("AEAD_AES_128_GCM")
+    gpols = profile_policies("AEAD_AES_128_GCM")
     rng = np.random.default_rng(1)
     key, salt = bytes(rng.integers(0, 256, 16, dtype=np.uint8)), bytes(rng.integers(0, 256, 12, dtype=np.uint8))
+    pols = gpols
+    if profile == "aescm":  # AES-CM + HMAC-SHA1 bundles of an engine that holds a GCM factory
+        pols = profile_policies("AES_CM_128_HMAC_SHA1_80")
+        (key, salt), = synth.keys(1, 1)
     for n in (int(x) for x in args.sizes.split(",")):
         eng = gcm_engine(n)
+        held = SRTPContextFactory(True, bytes(16), bytes(12), *gpols, engine=eng)  # noqa: F841 -- the engine's GCM key sets
         b = synth.rtp_bundle(n, n, PKT, seed=synth.SEED_BASE + n)
         seg0 = torch.from_numpy(b.seg).to(d)
         off = torch.from_numpy(b.off.view(np.int32)).to(d)
@@ -92,26 +109,35 @@ def sweep(args):
             t.close()
             return a.elapsed_time(e) * 1e3  # us
 
-        ms = {(r, rev): [] for r in ("lane", "wave") for rev in (False, True)}
+        ms = {(r, rev): [] for r in (old, new) for rev in (False, True)}
         for rev in (False, True):
             for i in range(args.warmup + args.steps):
-                for r in ("lane", "wave"):
+                for r in (old, new):
                     v = call(r, rev)
                     if i >= args.warmup:
                         ms[(r, rev)].append(v)
             if not rev:
                 sealed = [seg.clone(), ln.clone()]
         row = {"packets": n, "unit": "us"}
+        if (old, new) != ("lane", "wave"):
+            row["profile"] = profile
         wins = True
         for rev in (False, True):
             way = "unprotect" if rev else "protect"
-            lane, wave = summary(ms[("lane", rev)]), summary(ms[("wave", rev)])
-            row[way] = {"lane": lane, "wave": wave}
-            wins = wins and wave["median"] < lane["median"] - lane["spread"]
-        row["wave_wins"] = wins
+            so, sn = summary(ms[(old, rev)]), summary(ms[(new, rev)])
+            row[way] = {old: so, new: sn}
+            wins = wins and sn["median"] < so["median"] - so["spread"]
+        row[new + "_wins"] = wins
         rows.append(row)
         print(json.dumps(row), flush=True)
         eng.close()
+    return rows
+
+
+def small(args):
+    rows = []
+    for profile in args.profile.split(","):
+        rows += sweep(args, "chain", "small", profile)
     return rows
 
 
@@ -194,17 +220,20 @@ def once(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["sweep", "lone", "once"])
+    ap.add_argument("mode", choices=["sweep", "small", "lone", "once"])
     ap.add_argument("--out")
-    ap.add_argument("--sizes", default="1,4,16,64,256,1024,4096,8192")
+    ap.add_argument("--sizes", help="default: 1,4,16,64,256,1024,4096,8192 (sweep); 1,4,8,16,64,255 (small)")
+    ap.add_argument("--profile", default="gcm,aescm")
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--calls", type=int, default=3000)
     ap.add_argument("--warm-calls", type=int, default=200)
     ap.add_argument("--route", default="default,lane,wave")
     args = ap.parse_args()
+    if not args.sizes:
+        args.sizes = "1,4,8,16,64,255" if args.mode == "small" else "1,4,16,64,256,1024,4096,8192"
     import torch
-    rows = {"sweep": sweep, "lone": lone, "once": once}[args.mode](args)
+    rows = {"sweep": sweep, "small": small, "lone": lone, "once": once}[args.mode](args)
     if args.out:
         with open(args.out, "w") as f:
             json.dump({"device": torch.cuda.get_device_name(0), "mode": args.mode, "rows": rows}, f, indent=1)
