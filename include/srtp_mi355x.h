@@ -282,6 +282,38 @@ int32_t srtp_gcm_wave_max(void);
  * bundle off it.  Results must not change. */
 #define SRTP_DEBUG_FORCE_SMALL 0x40u
 int32_t srtp_small_aead_max(void);
+/* Unprotect of AES-GCM packets on the multi-kernel path opens a packet in one
+ * pass over its bytes: the pass before the walk checks the tag under the ROC
+ * guess and deciphers in the same trip (k_gcm<open>), the pass after the walk
+ * only repairs the packets whose verdict the walk overturned (k_gcm<fix>: a
+ * replay, a packet behind a throwing one under abort-on-error -- deciphered
+ * text put back as the ciphertext that came in).  Results are those of the
+ * two-pass route (tag check, walk, decipher) to the bit.  It is the default
+ * where it measured faster, clean and with 2.5 % replays and forgeries: on the
+ * wave route for bundles of srtp_gcm_open_wave_min() to srtp_gcm_open_wave_max()
+ * packets (4096 to 8192); on the lane route for bundles of
+ * srtp_gcm_open_lane_min() packets and more, which is INT32_MAX -- it won there
+ * only on clean bundles of 2^18, so the lane route stays on two passes.
+ * SRTP_DEBUG_NO_GCM_SPEC keeps every bundle on the two-pass route (A/B
+ * measurements, parity, fallback); SRTP_DEBUG_FORCE_GCM_SPEC puts every bundle
+ * of the multi-kernel path on the one-pass route, whichever kernels it takes
+ * (the parity tests; the only way to the lane kernels' one-pass modes).
+ * Neither flag changes which bundles k_small takes. */
+#define SRTP_DEBUG_NO_GCM_SPEC 0x80u
+#define SRTP_DEBUG_FORCE_GCM_SPEC 0x100u
+int32_t srtp_gcm_open_lane_min(void);
+int32_t srtp_gcm_open_wave_min(void);
+int32_t srtp_gcm_open_wave_max(void);
+/* opened: packets deciphered together with their tag check; restored: opened
+ * packets put back as ciphertext after the walk (not in srtp_stats.repaired);
+ * late: packets deciphered after the walk although the bundle took the
+ * one-pass route (a ROC the walk re-checked, a header whose extension length
+ * is negative).  Cumulative; all 0 on an engine without AES-GCM key sets and
+ * under SRTP_DEBUG_NO_GCM_SPEC. */
+typedef struct {
+    uint64_t opened, restored, late;
+} srtp_gcm_stats;
+int srtp_engine_gcm_stats(srtp_engine *e, srtp_gcm_stats *out);
 int srtp_engine_set_debug(srtp_engine *e, uint32_t flags);
 /* The AES-GCM switch (RFC 7714 profiles, see SRTP_AESGCM_ENCRYPTION): off on a
  * new engine.  While on, srtp_factory_create accepts the GCM policy shape for
@@ -684,6 +716,8 @@ int srtp_dispatch_set_context_state(srtp_dispatch *d, int32_t transformer, uint3
                                     int32_t forward, const srtp_ctx_state *st);
 /* srtp_stats summed over the shards */
 int srtp_dispatch_stats(srtp_dispatch *d, srtp_stats *out);
+/* srtp_gcm_stats summed over the shards */
+int srtp_dispatch_gcm_stats(srtp_dispatch *d, srtp_gcm_stats *out);
 /* Host time of srtp_dispatch_transform_host since creation, in ns: [0] plan
  * and split, [1] packing into the shards' pinned slots and enqueueing each
  * chunk's copies and kernels, [2] waiting for the
@@ -891,6 +925,24 @@ typedef struct {
 } srtp_gcm_job;
 int srtp_gcm_packet_job(int32_t kind, int32_t reverse, int32_t len, int32_t cap, int32_t header_len,
                         uint32_t flags, int32_t e_bit, srtp_gcm_job *out);
+/* The two rules of the one-pass open (host only; gcm_job.h, the text the GPU
+ * passes compile).  srtp_gcm_spec_ok: 1 when the pass before the walk may
+ * decipher an unprotect packet of this geometry -- its job has no status, it is
+ * not flagged DISCARD / SILENCE, it has data, SRTCP: E = 1, SRTP: header_len is
+ * at least the fixed header 12 + 4 CC (+ 4 with X) that byte0 announces (a
+ * negative extension length can give less, and the bytes the fix pass re-reads
+ * would lie inside the deciphered range); else 0; -1 for an unknown kind.
+ * srtp_gcm_fix_action: what the pass after the walk owes a packet, from
+ * whether it was deciphered before the walk (spec_done), its final status,
+ * whether it is to leave deciphered (wanted: status OK, no DISCARD / SILENCE,
+ * SRTCP: E = 1) and, for SRTP (rtp), the ROC guess g0 and the walk's ROC cw. */
+#define SRTP_GCM_FIX_NONE 0
+#define SRTP_GCM_FIX_RESTORE 1  /* the CTR pass again under the speculation's IV: ciphertext back */
+#define SRTP_GCM_FIX_DECIPHER 2 /* decipher under the walk's ROC / the index word */
+int32_t srtp_gcm_spec_ok(int32_t kind, int32_t len, int32_t cap, int32_t header_len, uint32_t flags,
+                         int32_t e_bit, uint32_t byte0);
+int32_t srtp_gcm_fix_action(int32_t spec_done, int32_t final_status, int32_t wanted, int32_t rtp, uint32_t g0,
+                            uint32_t cw);
 
 /* DTLS-SRTP keying (control plane, host only): what
  * DtlsPacketTransformer.initializeSRTPTransformer does after the handshake

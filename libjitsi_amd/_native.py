@@ -34,6 +34,9 @@ DEBUG_NO_SMALL = 0x8    # bundles of up to 255 packets off k_small (one launch p
 DEBUG_NO_GCM_WAVE = 0x10     # the AES-GCM passes always a lane per packet (k_gcm)
 DEBUG_FORCE_GCM_WAVE = 0x20  # ... always a wave per packet (k_gcm_wave)
 DEBUG_FORCE_SMALL = 0x40     # k_small's GCM instance up to 255 packets, past srtp_small_aead_max()
+DEBUG_NO_GCM_SPEC = 0x80     # GCM unprotect always in two passes (tag check, walk, decipher)
+DEBUG_FORCE_GCM_SPEC = 0x100  # ... always in one (k_gcm<open> / <fix>), on the multi-kernel path
+GCM_FIX_NONE, GCM_FIX_RESTORE, GCM_FIX_DECIPHER = 0, 1, 2  # srtp_gcm_fix_action (bits)
 GCM_BATCH_WAVE = 0x1         # srtp_aes_gcm_device_ex: a wave per packet
 ABI_VERSION = 3
 AGG_SEAL_IDLE = 0x1
@@ -82,6 +85,9 @@ EXPORTED = [
     "srtp_aes_gcm_device_ex", "srtp_gf128_mul", "srtp_gcm_hpowers", "srtp_gcm_wave_max",
     "srtp_small_aead_max",
     "srtp_trailer_room", "srtp_engine_trailer_room", "srtp_aggregator_trailer_room",
+    "srtp_engine_gcm_stats", "srtp_dispatch_gcm_stats", "srtp_gcm_open_lane_min", "srtp_gcm_open_wave_min",
+    "srtp_gcm_open_wave_max",
+    "srtp_gcm_spec_ok", "srtp_gcm_fix_action",
 ]
 STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 
@@ -158,6 +164,14 @@ class GcmJob(C.Structure):
     """srtp_gcm_job (include/srtp_mi355x.h)"""
     _fields_ = [(n, C.c_int32) for n in ("status", "new_len", "aad_len", "word_at", "word_aad",
                                          "data_at", "data_len", "tag_at", "decipher")]
+
+
+class GcmStats(C.Structure):
+    """srtp_gcm_stats (include/srtp_mi355x.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("opened", "restored", "late")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 DTLS_AEAD = 0x1
@@ -287,6 +301,18 @@ def lib() -> C.CDLL:
     L.srtp_gcm_wave_max.restype = i32
     L.srtp_small_aead_max.argtypes = []
     L.srtp_small_aead_max.restype = i32
+    L.srtp_gcm_open_lane_min.argtypes = []
+    L.srtp_gcm_open_lane_min.restype = i32
+    L.srtp_gcm_open_wave_min.argtypes = []
+    L.srtp_gcm_open_wave_min.restype = i32
+    L.srtp_gcm_open_wave_max.argtypes = []
+    L.srtp_gcm_open_wave_max.restype = i32
+    L.srtp_engine_gcm_stats.argtypes = [vp, C.POINTER(GcmStats)]
+    L.srtp_dispatch_gcm_stats.argtypes = [vp, C.POINTER(GcmStats)]
+    L.srtp_gcm_spec_ok.argtypes = [i32, i32, i32, i32, u32, i32, u32]
+    L.srtp_gcm_spec_ok.restype = i32
+    L.srtp_gcm_fix_action.argtypes = [i32, i32, i32, i32, u32, u32]
+    L.srtp_gcm_fix_action.restype = i32
     L.srtp_trailer_room.argtypes = [i32]
     L.srtp_trailer_room.restype = i32
     L.srtp_engine_trailer_room.argtypes = [vp]

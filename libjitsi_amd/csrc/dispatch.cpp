@@ -1101,4 +1101,19 @@ int srtp_dispatch_stats(srtp_dispatch *d, srtp_stats *out) {
     });
 }
 
+int srtp_dispatch_gcm_stats(srtp_dispatch *d, srtp_gcm_stats *out) {
+    if (!d || !out) return SRTP_EINVAL;
+    std::lock_guard<FairMutex> g(d->mu);
+    memset(out, 0, sizeof *out);
+    return each(d, [&](srtp_engine *e) {
+        srtp_gcm_stats s;
+        const int rc = srtp_engine_gcm_stats(e, &s);
+        if (rc != SRTP_OK) return rc;
+        out->opened += s.opened;
+        out->restored += s.restored;
+        out->late += s.late;
+        return SRTP_OK;
+    });
+}
+
 } // extern "C"

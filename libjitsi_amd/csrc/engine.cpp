@@ -829,6 +829,14 @@ static int transform_locked(srtp_engine *e, int32_t reverse, const int32_t *tids
     a.gcmpow = e->d_gcmpow;
     a.gcm_route = (e->dbg & SRTP_DEBUG_NO_GCM_WAVE) ? kGcmRouteLane : (e->dbg & SRTP_DEBUG_FORCE_GCM_WAVE) ? kGcmRouteWave : 0;
     a.has_gcm = e->n_gcm ? 1 : 0;
+    // the one-pass open: where the sweep made it the default on the route this
+    // bundle takes (srtp_kernels.h), or as the hooks say
+    const bool gcm_wave = a.gcm_route ? a.gcm_route == kGcmRouteWave : n <= kGcmWaveMax; // launch_gcm's rule
+    const bool gcm_spec = !e->n_gcm || (e->dbg & SRTP_DEBUG_NO_GCM_SPEC) ? false
+                          : (e->dbg & SRTP_DEBUG_FORCE_GCM_SPEC)         ? true
+                          : gcm_wave ? n >= kGcmOpenWaveMin && n <= kGcmOpenWaveMax
+                                     : n >= kGcmOpenLaneMin;
+    if (gcm_spec) a.gcm_route |= kGcmRouteSpec;
     a.factories = e->d_factories;
     a.transformers = e->d_transformers;
     a.ctx_keys = e->d_ctx_keys;
@@ -936,7 +944,8 @@ static int transform_locked(srtp_engine *e, int32_t reverse, const int32_t *tids
         HIPCHK(e, launch_unprotect(a, s));
         if (a.small_ctr) HIPCHK(e, launch_ctr_small(a, s)); // the speculative decryption
         if (e->n_skein) HIPCHK(e, launch_skein(a, s));
-        if (e->n_gcm) HIPCHK(e, launch_gcm(a, 1, s)); // tag check under the ROC guess
+        // tag check under the ROC guess (3: and the decipher, in the same trip)
+        if (e->n_gcm) HIPCHK(e, launch_gcm(a, gcm_spec ? 3 : 1, s));
     }
     {
         StageTimer t(e, s, SRTP_STAGE_WALK);
@@ -959,7 +968,8 @@ static int transform_locked(srtp_engine *e, int32_t reverse, const int32_t *tids
         StageTimer t(e, s, SRTP_STAGE_DECRYPT);
         HIPCHK(e, launch_unprotect_fix(a, s));
         if (e->n_ext) HIPCHK(e, launch_ext(a, s));
-        if (e->n_gcm) HIPCHK(e, launch_gcm(a, 2, s)); // the accepted packets deciphered
+        // the accepted packets deciphered (4: only the verdicts the walk overturned repaired)
+        if (e->n_gcm) HIPCHK(e, launch_gcm(a, gcm_spec ? 4 : 2, s));
     } else {
         StageTimer t(e, s, SRTP_STAGE_PROTECT);
         if (a.small_ctr) HIPCHK(e, launch_ctr_small(a, s)); // the keystream, then k_protect MACs
@@ -1284,6 +1294,23 @@ int srtp_engine_stats(srtp_engine *e, srtp_stats *out) {
     return SRTP_OK;
 }
 
+int srtp_engine_gcm_stats(srtp_engine *e, srtp_gcm_stats *out) {
+    if (!e || !out) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    GUARD(e);
+    int rc = quiesce(e);
+    if (rc != SRTP_OK) return rc;
+    std::vector<unsigned long long> c((size_t)kCountReplicas * kCtrStride);
+    HIPCHK(e, hipMemcpy(c.data(), e->d_counters, c.size() * sizeof(c[0]), hipMemcpyDeviceToHost));
+    memset(out, 0, sizeof *out);
+    for (int r = 0; r < kCountReplicas; r++) {
+        out->opened += c[(size_t)r * kCtrStride + kCtrGcmOpened];
+        out->restored += c[(size_t)r * kCtrStride + kCtrGcmRestored];
+        out->late += c[(size_t)r * kCtrStride + kCtrGcmLate];
+    }
+    return SRTP_OK;
+}
+
 int32_t srtp_device_count(void) {
     int n = 0;
     return hipGetDeviceCount(&n) == hipSuccess ? (int32_t)n : 0;
@@ -1291,7 +1318,8 @@ int32_t srtp_device_count(void) {
 
 int srtp_engine_set_debug(srtp_engine *e, uint32_t flags) {
     if (!e || (flags & ~(SRTP_DEBUG_FORCE_CHAIN_STALL | SRTP_DEBUG_FORCE_WIDE | SRTP_DEBUG_NO_WIDE | SRTP_DEBUG_NO_SMALL |
-                        SRTP_DEBUG_NO_GCM_WAVE | SRTP_DEBUG_FORCE_GCM_WAVE | SRTP_DEBUG_FORCE_SMALL)))
+                        SRTP_DEBUG_NO_GCM_WAVE | SRTP_DEBUG_FORCE_GCM_WAVE | SRTP_DEBUG_FORCE_SMALL |
+                        SRTP_DEBUG_NO_GCM_SPEC | SRTP_DEBUG_FORCE_GCM_SPEC)))
         return SRTP_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     e->dbg = flags;
@@ -1452,6 +1480,24 @@ int srtp_gcm_hpowers(const uint8_t h[16], uint8_t out[1024]) {
 
 int32_t srtp_gcm_wave_max(void) { return (int32_t)kGcmWaveMax; }
 int32_t srtp_small_aead_max(void) { return (int32_t)kSmallGcmMax; }
+int32_t srtp_gcm_open_lane_min(void) { return (int32_t)kGcmOpenLaneMin; }
+int32_t srtp_gcm_open_wave_min(void) { return (int32_t)kGcmOpenWaveMin; }
+int32_t srtp_gcm_open_wave_max(void) { return (int32_t)kGcmOpenWaveMax; }
+
+int32_t srtp_gcm_spec_ok(int32_t kind, int32_t len, int32_t cap, int32_t header_len, uint32_t flags, int32_t e_bit,
+                         uint32_t byte0) {
+    if (kind != SRTP_KIND_RTP && kind != SRTP_KIND_RTCP) return SRTP_EINVAL;
+    const GcmJob j = gcm_packet_job(kind, 1, len, cap, header_len, flags, e_bit ? 1 : 0);
+    return gcm_spec_ok(kind, j, header_len, byte0, e_bit ? 1 : 0);
+}
+
+int32_t srtp_gcm_fix_action(int32_t spec_done, int32_t final_status, int32_t wanted, int32_t rtp, uint32_t g0,
+                            uint32_t cw) {
+    static_assert(SRTP_GCM_FIX_NONE == kGcmFixNone && SRTP_GCM_FIX_RESTORE == kGcmFixRestore &&
+                      SRTP_GCM_FIX_DECIPHER == kGcmFixDecipher && SRTP_STATUS_OK == 0,
+                  "gcm_job.h restates these constants");
+    return gcm_fix_action(spec_done ? 1 : 0, final_status, wanted ? 1 : 0, rtp ? 1 : 0, g0, cw);
+}
 
 int32_t srtp_trailer_room(int32_t aead) { return (int32_t)trailer_room(aead); }
 

@@ -139,4 +139,47 @@ SRTP_GCM_HD inline GcmJob gcm_packet_job(int kind, int reverse, int L, int cap, 
     return j;
 }
 
+// ---- the one-pass open (k_gcm<kGcmOpen> / <kGcmFix>, the wave kernels' twins)
+// The pass before the walk checks a packet's tag under the ROC guess g0 (SRTCP:
+// under its index word) and, where gcm_spec_ok allows, deciphers it in the same
+// trip; the pass after the walk compares that with the walk's verdict and
+// repairs the misses (gcm_fix_action).  Both rules in one place, for the
+// kernels and for tools/gcm_open_check.cpp.
+
+// May the open pass decipher this unprotect packet before the walk?  j: its
+// job (gcm_packet_job with reverse = 1 and, for SRTCP, the word's E bit); h: the
+// RTP header length the job was asked with; b0: the packet's first byte (CC in
+// bits 0-3, X in bit 4); e_bit: SRTCP's E bit.  The SRTP rule is k_unprotect's:
+// a negative extension length can give a header length below the fixed header
+// 12 + 4 CC (+ 4 with X), which puts bytes the fix pass re-reads (byte 0, the
+// extension length, the SSRC) inside the deciphered range -- such a packet is
+// only verified, and deciphered after the walk.
+SRTP_GCM_HD inline int gcm_spec_ok(int kind, const GcmJob &j, int32_t h, uint32_t b0, int e_bit) {
+    if (j.status != kGcmNoStatus || !j.decipher || j.data_len <= 0) return 0;
+    if (kind != 0) return e_bit ? 1 : 0;
+    const int fixed = 12 + 4 * (int)(b0 & 0x0fu) + ((b0 & 0x10u) ? 4 : 0);
+    return h != kGcmHdrThrow && h >= fixed ? 1 : 0;
+}
+
+// What the fix pass owes a packet: bit 0 (kGcmFixRestore) the CTR pass again
+// under the IV of the speculation (g0 / the index word) over the length the
+// packet came with, which puts the ciphertext back; bit 1 (kGcmFixDecipher)
+// the decipher under the walk's ROC w_cw, today's k_gcm<kGcmDecipher> step.
+constexpr int kGcmFixNone = 0, kGcmFixRestore = 1, kGcmFixDecipher = 2, kGcmFixRestoreDecipher = 3;
+
+// spec_done: the open pass deciphered the packet (its tag matched under g0).
+// wanted: final status OK, the job's `decipher` set and, for SRTCP, E = 1.
+// rtp: SRTP (g0 and cw are ROCs; for SRTCP they play no part).  A speculation
+// that the walk confirms under another ROC cannot happen -- a tag that matches
+// under g0 proves g0 -- and still gets restore, then decipher.
+SRTP_GCM_HD inline int gcm_fix_action(int spec_done, int final_status, int wanted, int rtp, uint32_t g0,
+                                      uint32_t cw) {
+    const bool want = wanted && final_status == 0;
+    if (spec_done) {
+        if (!want) return kGcmFixRestore;
+        return rtp && g0 != cw ? kGcmFixRestoreDecipher : kGcmFixNone;
+    }
+    return want ? kGcmFixDecipher : kGcmFixNone;
+}
+
 } // namespace srtp

@@ -101,7 +101,8 @@ struct BundleArgs {
     // selects the walk's GCM instances and the k_gcm passes
     const GcmKeys *gcmkeys;
     int32_t has_gcm;
-    int32_t gcm_route;     // launch_gcm: 0 by bundle size (kGcmWaveMax), else kGcmRoute* (test hooks)
+    int32_t gcm_route;     // launch_gcm: bits 0-1: 0 by bundle size (kGcmWaveMax), else kGcmRoute* (test hooks);
+                           // kGcmRouteSpec: unprotect in one pass (launch_gcm modes 3 and 4), else verify + decipher
     const GcmPow *gcmpow;  // [keysets] beside gcmkeys: the powers of H (k_gcm_wave)
 };
 
@@ -149,7 +150,32 @@ hipError_t launch_skein(const BundleArgs &a, hipStream_t s);
 // protect and unprotect; it did at every size of the sweep, by 3.7-4.3x up to
 // 64 packets and by 6-18 % at 8192.
 constexpr uint32_t kGcmWaveMax = 8192u;
-constexpr int32_t kGcmRouteLane = 1, kGcmRouteWave = 2;
+constexpr int32_t kGcmRouteLane = 1, kGcmRouteWave = 2, kGcmRouteMask = 3, kGcmRouteSpec = 4;
+// Unprotect in one pass over the packet bytes (kGcmRouteSpec in BundleArgs::gcm_route,
+// which no kernel reads: the struct every kernel takes by value is the parent's): mode 3
+// (open) in mode 1's place checks the tag under the ROC guess and deciphers in
+// the same trip where gcm_spec_ok (gcm_job.h) allows; mode 4 (fix) in mode 2's
+// place repairs the packets whose verdict the walk overturned (gcm_fix_action)
+// and is otherwise a launch whose workgroups leave at once.  Results are those
+// of modes 1 and 2 to the bit.  It is the default at the sizes of the measured
+// sweep (profiles/gcm_open/sweep.json) at which its median lies below the
+// two-pass route's by more than that route's own p90 - p10, for GCM-128 and
+// GCM-256, on a clean bundle and on one with 2.5 % replays and forgeries:
+//   wave route  4096 and 8192 packets, by 9-11 % clean and 2-5 % with the mix.
+//               Below that a bundle is bound by its launches' latency, and one
+//               packet to repair costs the fix pass what the whole decipher
+//               pass costs: 5-8 % slower at 256 and 1024 with the mix (5-7 %
+//               faster clean there and at 1, 16 and 64).
+//   lane route  nowhere: 2-7 % faster on a clean bundle of 2^18, but 20-36 %
+//               slower with the mix (a wave's 64 lanes wait for the one that
+//               repairs), and 5-73 % slower at 2^14 and 2^16 (one lane's serial
+//               AES + GHASH chain, where two shorter passes overlap better).
+//               Its code is reached by SRTP_DEBUG_FORCE_GCM_SPEC alone.
+// SRTP_DEBUG_NO_GCM_SPEC keeps every bundle on modes 1 and 2, _FORCE_GCM_SPEC
+// puts every bundle of the multi-kernel path on modes 3 and 4.
+constexpr uint32_t kGcmOpenLaneMin = 0x7FFFFFFFu; // no bundle is that large (kRecIdxMask): never
+constexpr uint32_t kGcmOpenWaveMin = 4096u;
+constexpr uint32_t kGcmOpenWaveMax = kGcmWaveMax;
 hipError_t launch_gcm(const BundleArgs &a, int mode, hipStream_t s);
 hipError_t launch_walk(const BundleArgs &a, int limit_pass, hipStream_t s);
 hipError_t launch_protect(const BundleArgs &a, hipStream_t s);

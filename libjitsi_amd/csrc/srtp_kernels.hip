@@ -4936,21 +4936,26 @@ struct GcmPkt {
     int tail_len = 0;
 };
 
-enum { kGcmSeal = 0, kGcmVerify = 1, kGcmDecipher = 2 };
+enum { kGcmSeal = 0, kGcmVerify = 1, kGcmDecipher = 2, kGcmOpen = 3, kGcmFix = 4 };
 
 // The whole AEAD for one lane's packet, in one of three modes:
 //   seal      AES-CTR (inc32 from counter 2) over the data in place, GHASH over
 //             AAD || ciphertext || lengths, tag = GHASH ^ E_K(IV || 1);
 //   verify    that tag over the data as it stands (ciphertext), nothing written;
-//   decipher  the AES-CTR pass alone (tag[] untouched).
+//   decipher  the AES-CTR pass alone (tag[] untouched);
+//   open      verify and decipher in one trip, shaped like seal: each
+//             ciphertext block is loaded once, absorbed into GHASH, XORed with
+//             its keystream and stored -- stored only with `write` set (a
+//             runtime flag: a lane that must not decipher yet runs the same
+//             trip and stores nothing).  The caller compares the tag.
 // tag[]: the 16 tag bytes as little-endian words.  Cipher: encrypt2() of two
 // blocks, as k_ext's ciphers; the mask block E_K(IV || 1) shares the first
 // pair with counter 2.  Touches no byte outside [aad, aad + aad_len + len).
-// mask_out (verify mode, may be null): E_K(IV || 1), so that a caller can keep
-// GHASH ^ received tag for a re-check under another IV.
+// mask_out (verify and open modes, may be null): E_K(IV || 1), so that a caller
+// can keep GHASH ^ received tag for a re-check under another IV.
 template <int MODE, class Cipher>
 __device__ __forceinline__ void gcm_packet(const Cipher &cipher, const uint32_t *tab, const GcmPkt &j,
-                                           uint32_t tag[4], uint32_t *mask_out = nullptr) {
+                                           uint32_t tag[4], uint32_t *mask_out = nullptr, bool write = true) {
     uint8_t *data = j.aad + j.aad_len;
     const int nb = (j.len + 15) >> 4;
     uint64_t zh = 0ull, zl = 0ull;
@@ -4978,20 +4983,21 @@ __device__ __forceinline__ void gcm_packet(const Cipher &cipher, const uint32_t 
                 const int m = min(16, j.len - 16 * b);
                 uint32_t d[4];
                 gcm_load(data + 16 * b, m, d);
+                if (MODE == kGcmOpen) gcm_absorb(tab, zh, zl, d); // the ciphertext, zero-padded by the load
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const int keep = m - 4 * k; // bytes of word k inside the data
                     const uint32_t km = keep >= 4 ? ~0u : (keep <= 0 ? 0u : (1u << (8 * keep)) - 1u);
                     d[k] = (d[k] ^ ks[k]) & km;
                 }
-                gcm_store(data + 16 * b, m, d);
+                if (MODE != kGcmOpen || write) gcm_store(data + 16 * b, m, d);
                 if (MODE == kGcmSeal) gcm_absorb(tab, zh, zl, d);
             }
         }
     }
     if (MODE == kGcmDecipher) return;
     gcm_mult_xor(tab, zh, zl, (uint64_t)(j.aad_len + j.tail_len) * 8ull, (uint64_t)j.len * 8ull);
-    if (MODE == kGcmVerify && mask_out) {
+    if ((MODE == kGcmVerify || MODE == kGcmOpen) && mask_out) {
 #pragma unroll
         for (int k = 0; k < 4; k++) mask_out[k] = mask[k];
     }
@@ -5169,13 +5175,181 @@ __device__ __forceinline__ void gcm_one(const BundleArgs &a, const char *__restr
     }
 }
 
+// ---- the one-pass open: kGcmOpen before the walk, kGcmFix after it
+// (kGcmRouteSpec; gcm_job.h has the two rules, gcm_spec_ok and
+// gcm_fix_action).  The open pass is the verify pass -- same work list, same
+// gok[2p + 1] and S -- that also deciphers, in the same trip, every packet
+// gcm_spec_ok allows, and keeps the deciphered text only where the tag matched
+// under g0.  It records that (kSpecGcm) and the length the packet came with in
+// spec[p], whose low bits k_unprotect wrote earlier in this bundle and which
+// k_unprotect_fix, the walk and k_ctr_small test bit by bit.  The fix pass
+// then has work only for the packets whose verdict the walk overturned.
+
+// An unprotect packet of GCM key set ks_u as it came in, L bytes long: its job,
+// the AEAD's view without the IV, and what gcm_spec_ok and the IV need.  Every
+// byte read here -- byte 0, the extension length, SEQ, the SSRC, SRTCP's word
+// behind the tag -- lies outside the range a speculation writes (gcm_spec_ok).
+// false: the lengths alone settle the packet, nothing to do.
+struct GcmView {
+    GcmJob j;
+    GcmPkt gp;
+    uint8_t *pkt;
+    bool rtp;
+    int spec_ok;
+    uint32_t ssrc_le, seq, word;
+};
+__device__ __forceinline__ bool gcm_view(const BundleArgs &a, uint32_t ks_u, uint32_t p, int L, GcmView &v) {
+    const KeySet *ks = a.keysets + ks_u;
+    v.rtp = sgpr((uint32_t)ks->kind) == (uint32_t)SRTP_KIND_RTP;
+    const uint32_t cap_u = a.cap[p];
+    if (cap_u > 65535u) return false; // k_parse refused such a packet
+    const int C = (int)cap_u;
+    if (L < 12 || L > C) return false; // the job would say so too; no header byte is read before this
+    v.pkt = a.seg + a.off[p];
+    const uint32_t fl = a.flags ? a.flags[p] : 0u;
+    v.gp.aad = v.pkt;
+    v.word = 0u;
+    v.seq = 0u;
+    if (v.rtp) {
+        const uint32_t w0 = *reinterpret_cast<const uint32_t *>(v.pkt);     // V/P/X/CC, M/PT, SEQ
+        v.ssrc_le = *reinterpret_cast<const uint32_t *>(v.pkt + 8);         // SSRC
+        const int32_t h = rtp_header_len(v.pkt, w0 & 0xffu, C);
+        v.j = gcm_packet_job(0, 1, L, C, h, fl, 1);
+        if (v.j.status != kGcmNoStatus) return false;
+        v.seq = bswap(w0) & 0xffffu;
+        v.spec_ok = gcm_spec_ok(0, v.j, h, w0 & 0xffu, 1);
+    } else {
+        v.ssrc_le = *reinterpret_cast<const uint32_t *>(v.pkt + 4); // SSRC
+        v.j = gcm_packet_job(1, 1, L, C, 0, 0u, 1); // where the word lies does not depend on E
+        if (v.j.status != kGcmNoStatus) return false;
+        v.word = ld_be32(v.pkt + v.j.word_at);
+        v.j = gcm_packet_job(1, 1, L, C, 0, 0u, (int)(v.word >> 31));
+        if (v.j.status != kGcmNoStatus) return false;
+        v.spec_ok = gcm_spec_ok(1, v.j, 0, 0u, (int)(v.word >> 31));
+        v.gp.tail = bswap(v.word);
+        v.gp.tail_len = 4;
+    }
+    v.gp.aad_len = v.j.aad_len;
+    v.gp.len = v.j.data_len;
+    return true;
+}
+// The IV: SRTP's under ROC `roc`, SRTCP's under the packet's own index word.
+__device__ __forceinline__ void gcm_view_iv(const GcmKeys *gk, GcmView &v, uint32_t roc) {
+    const uint32_t salt[3] = {sgpr(gk->salt[0]), sgpr(gk->salt[1]), sgpr(gk->salt[2])};
+    if (v.rtp) gcm_iv_rtp(salt, v.ssrc_le, roc, v.seq, v.gp.iv);
+    else gcm_iv_rtcp(salt, v.ssrc_le, v.word, v.gp.iv);
+}
+
+// The open pass's first stores for packet p: the verify result cleared, and
+// spec[p] = k_unprotect's bits | the length the packet came with -- before any
+// return, so that the fix pass never meets a stale kSpecGcm.  Returns that word.
+__device__ __forceinline__ uint32_t gcm_open_begin(const BundleArgs &a, uint32_t p, bool writer) {
+    const uint32_t len_u = a.len[p];
+    const uint32_t sw = (a.spec[p] & kSpecLowMask) | (len_u <= 65535u ? len_u << 16 : 0u);
+    if (writer) {
+        a.gok[2 * (size_t)p + 1] = 0u;
+        a.spec[p] = sw;
+    }
+    return sw;
+}
+
+// k_gcm<kGcmOpen>'s lane: true when the packet was deciphered and stays so.
+__device__ __forceinline__ bool gcm_open_one(const BundleArgs &a, const char *__restrict__ lds, const TeBase &tb,
+                                             const uint32_t *tab, uint32_t ks_u, uint32_t p) {
+    const GcmKeys *gk = a.gcmkeys + ks_u;
+    const uint32_t sw = gcm_open_begin(a, p, true);
+    GcmView v;
+    if (!gcm_view(a, ks_u, p, (int)(sw >> 16), v)) return false;
+    gcm_view_iv(gk, v, a.gok[2 * (size_t)p]);
+    RoundKeys256 rk;
+    load_rk256_uniform(gk->rk, rk);
+    const GcmBatchCipher cipher{lds, tb, rk, sgpr((uint32_t)gk->nr) == 14u};
+    const bool write = v.spec_ok != 0;
+    uint32_t tag[4], mask[4], got[4];
+    gcm_load(v.pkt + v.j.tag_at, 16, got); // the tag lies behind the data: the trip does not touch it
+    gcm_packet<kGcmOpen>(cipher, tab, v.gp, tag, mask, write);
+    uint32_t *S = a.mid + 5 * (size_t)p;
+    uint32_t diff = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        diff |= tag[k] ^ got[k];
+        S[k] = tag[k] ^ mask[k] ^ got[k];
+    }
+    a.gok[2 * (size_t)p + 1] = diff == 0u ? 1u : 0u;
+    if (!write) return false;
+    if (diff != 0u) { // rare: the same CTR pass puts the ciphertext back before the kernel ends
+        gcm_packet<kGcmDecipher>(cipher, tab, v.gp, tag);
+        return false;
+    }
+    a.spec[p] = sw | kSpecGcm;
+    return true;
+}
+
+// What the fix pass owes packet p (gcm_fix_action; kGcmFixNone: nothing, also
+// for a packet of no GCM key set), from the packet index, p_slot, the key
+// set's mark and kind, the final status, the flags, spec[p], g0 and w_cw alone:
+// no packet pointer or table index is formed before.  ks_id: its key set.
+__device__ __forceinline__ int gcm_fix_todo(const BundleArgs &a, uint32_t p, uint32_t &ks_id) {
+    ks_id = 0u;
+    if (p >= a.n) return kGcmFixNone;
+    const uint32_t slot = a.p_slot[p];
+    if (slot == kNoSlot) return kGcmFixNone;
+    ks_id = a.ctx[slot].ks;
+    if (a.keysets[ks_id].pad != kGcmMark) return kGcmFixNone;
+    const bool rtp = a.keysets[ks_id].kind == SRTP_KIND_RTP;
+    const uint32_t sw = a.spec[p], cw = a.w_cw[p], g0 = a.gok[2 * (size_t)p];
+    const int32_t st = a.status[p];
+    const uint32_t fl = a.flags ? a.flags[p] : 0u;
+    // accepted SRTCP: the walk left the packet's E|index word in w_cw
+    const bool wanted = st == SRTP_STATUS_OK && (rtp ? !(fl & kGcmFlagNoDecipher) : (cw >> 31) != 0u);
+    return gcm_fix_action((sw & kSpecGcm) ? 1 : 0, st, wanted ? 1 : 0, rtp ? 1 : 0, g0, cw);
+}
+
+// k_gcm<kGcmFix>'s lane.  Every offset from gcm_packet_job under the length
+// the open pass recorded; a.len and w_len play no part.  restored / late: the
+// counters' increments.
+__device__ __forceinline__ void gcm_fix_one(const BundleArgs &a, const char *__restrict__ lds, const TeBase &tb,
+                                            const uint32_t *tab, uint32_t ks_u, uint32_t p, int act, bool &restored,
+                                            bool &late) {
+    const GcmKeys *gk = a.gcmkeys + ks_u;
+    GcmView v;
+    if (!gcm_view(a, ks_u, p, (int)(a.spec[p] >> 16), v)) return;
+    RoundKeys256 rk;
+    load_rk256_uniform(gk->rk, rk);
+    const GcmBatchCipher cipher{lds, tb, rk, sgpr((uint32_t)gk->nr) == 14u};
+    uint32_t tag[4];
+    if ((act & kGcmFixRestore) && v.spec_ok) { // the speculation's own IV and range
+        gcm_view_iv(gk, v, a.gok[2 * (size_t)p]);
+        gcm_packet<kGcmDecipher>(cipher, tab, v.gp, tag);
+        restored = true;
+    }
+    if ((act & kGcmFixDecipher) && v.j.decipher && (v.rtp || (v.word >> 31))) {
+        gcm_view_iv(gk, v, a.w_cw[p]);
+        gcm_packet<kGcmDecipher>(cipher, tab, v.gp, tag);
+        late = v.j.data_len > 0;
+    }
+}
+
+// One wave-aggregated add to this workgroup's replica of counter `ctr`.
+__device__ __forceinline__ void gcm_count(const BundleArgs &a, int ctr, bool hit) {
+    const unsigned long long m = __ballot(hit);
+    if (m != 0ull && (threadIdx.x & 63u) == 0u)
+        atomicAdd(&a.counters[(blockIdx.x % (uint32_t)kCountReplicas) * kCtrStride + ctr],
+                  (unsigned long long)__popcll(m));
+}
+
 template <int MODE>
 __global__ __launch_bounds__(kGcmBlock) void k_gcm(BundleArgs a) {
     __shared__ uint32_t s_te[kTeWords + (kGcmBlock / 64) * kGcmTabWords]; // the image stays at LDS 0
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     bool todo = false;
     uint32_t ks_id = 0u;
-    if (p < a.n && (MODE == kGcmVerify || a.status[p] == SRTP_STATUS_OK)) {
+    int act = kGcmFixNone;
+    bool n_open = false, n_restored = false, n_late = false;
+    if constexpr (MODE == kGcmFix) {
+        act = gcm_fix_todo(a, p, ks_id);
+        todo = act != kGcmFixNone;
+    } else if (p < a.n && (MODE == kGcmVerify || MODE == kGcmOpen || a.status[p] == SRTP_STATUS_OK)) {
         const uint32_t slot = a.p_slot[p];
         if (slot != kNoSlot) {
             ks_id = a.ctx[slot].ks;
@@ -5195,10 +5369,17 @@ __global__ __launch_bounds__(kGcmBlock) void k_gcm(BundleArgs a) {
         tab[lane] = reinterpret_cast<const uint32_t *>(a.gcmkeys[ks_u].htab)[lane];
         walk_sync(); // the wave's own LDS writes, before its lanes read the table
         if (todo && ks_id == ks_u) {
-            gcm_one<MODE>(a, lds, tb, tab, ks_u, p);
+            if constexpr (MODE == kGcmOpen) n_open = gcm_open_one(a, lds, tb, tab, ks_u, p);
+            else if constexpr (MODE == kGcmFix) gcm_fix_one(a, lds, tb, tab, ks_u, p, act, n_restored, n_late);
+            else gcm_one<MODE>(a, lds, tb, tab, ks_u, p);
             todo = false;
         }
         walk_sync(); // the table is rewritten by the next pass
+    }
+    if constexpr (MODE == kGcmOpen) gcm_count(a, kCtrGcmOpened, n_open);
+    if constexpr (MODE == kGcmFix) {
+        gcm_count(a, kCtrGcmRestored, n_restored);
+        gcm_count(a, kCtrGcmLate, n_late);
     }
 }
 
@@ -5545,17 +5726,89 @@ __device__ __forceinline__ void gcm_wave_pass(const BundleArgs &a, const uint32_
 // Whether it has work is wave-uniform, as is the key set, so there is no
 // key-set loop; a workgroup none of whose packets has GCM work leaves before
 // filling the image.
+// The one-pass open with a wave per packet (k_gcm's kGcmOpen / kGcmFix, the
+// same scratch word and the same two rules): the verify step, then -- the tag
+// matched under g0 and gcm_spec_ok holds, both wave-uniform -- the decipher
+// step under g0 in the same launch, around one image fill instead of two.
+__device__ __forceinline__ void gcm_wave_open(const BundleArgs &a, const uint32_t *s_te, uint32_t p, uint32_t ks_id,
+                                              uint32_t lane) {
+    const uint32_t ks_u = sgpr(ks_id);
+    const GcmKeys *gk = a.gcmkeys + ks_u;
+    const uint32_t sw = gcm_open_begin(a, p, lane == 0u);
+    GcmView v;
+    if (!gcm_view(a, ks_u, p, (int)(sw >> 16), v)) return;
+    gcm_view_iv(gk, v, a.gok[2 * (size_t)p]);
+    const uint32_t *pw = reinterpret_cast<const uint32_t *>(a.gcmpow[ks_u].pow);
+    RoundKeys256 rk;
+    load_rk256_uniform(gk->rk, rk);
+    const GcmBatchCipher cipher{reinterpret_cast<const char *>(s_te), te_base(), rk, sgpr((uint32_t)gk->nr) == 14u};
+    uint32_t tag[4], mask[4], got[4];
+    gcm_packet_wave<kGcmVerify>(cipher, pw, v.gp, lane, tag, mask);
+    gcm_load(v.pkt + v.j.tag_at, 16, got); // every lane: the verdict is wave-uniform
+    uint32_t diff = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; k++) diff |= tag[k] ^ got[k];
+    if (lane == 0u) {
+        uint32_t *S = a.mid + 5 * (size_t)p;
+#pragma unroll
+        for (int k = 0; k < 4; k++) S[k] = tag[k] ^ mask[k] ^ got[k];
+        a.gok[2 * (size_t)p + 1] = diff == 0u ? 1u : 0u;
+    }
+    const bool go = (uint32_t)__shfl((int)diff, 0) == 0u && v.spec_ok != 0;
+    if (!go) return;
+    gcm_packet_wave<kGcmDecipher>(cipher, pw, v.gp, lane, tag);
+    if (lane == 0u) {
+        a.spec[p] = sw | kSpecGcm;
+        atomicAdd(&a.counters[(blockIdx.x % (uint32_t)kCountReplicas) * kCtrStride + kCtrGcmOpened], 1ull);
+    }
+}
+
+__device__ __forceinline__ void gcm_wave_fix(const BundleArgs &a, const uint32_t *s_te, uint32_t p, uint32_t ks_id,
+                                             uint32_t lane, int act) {
+    const uint32_t ks_u = sgpr(ks_id);
+    const GcmKeys *gk = a.gcmkeys + ks_u;
+    GcmView v;
+    if (!gcm_view(a, ks_u, p, (int)(a.spec[p] >> 16), v)) return;
+    const uint32_t *pw = reinterpret_cast<const uint32_t *>(a.gcmpow[ks_u].pow);
+    RoundKeys256 rk;
+    load_rk256_uniform(gk->rk, rk);
+    const GcmBatchCipher cipher{reinterpret_cast<const char *>(s_te), te_base(), rk, sgpr((uint32_t)gk->nr) == 14u};
+    unsigned long long *ctr = a.counters + (blockIdx.x % (uint32_t)kCountReplicas) * kCtrStride;
+    uint32_t tag[4];
+    if ((act & kGcmFixRestore) && v.spec_ok) { // the speculation's own IV and range
+        gcm_view_iv(gk, v, a.gok[2 * (size_t)p]);
+        gcm_packet_wave<kGcmDecipher>(cipher, pw, v.gp, lane, tag);
+        if (lane == 0u) atomicAdd(&ctr[kCtrGcmRestored], 1ull);
+        walk_sync();
+    }
+    if ((act & kGcmFixDecipher) && v.j.decipher && (v.rtp || (v.word >> 31))) {
+        gcm_view_iv(gk, v, a.w_cw[p]);
+        gcm_packet_wave<kGcmDecipher>(cipher, pw, v.gp, lane, tag);
+        if (lane == 0u && v.j.data_len > 0) atomicAdd(&ctr[kCtrGcmLate], 1ull);
+    }
+}
+
 template <int MODE>
 __global__ __launch_bounds__(kGcmWaveBlock) void k_gcm_wave(BundleArgs a) {
     __shared__ uint32_t s_te[kTeWords]; // the image stays at LDS 0
     const uint32_t p = blockIdx.x * (uint32_t)(kGcmWaveBlock / 64) + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63u;
     uint32_t ks_id;
-    const bool todo = gcm_wave_todo<MODE>(a, p, ks_id);
-    if (!__syncthreads_or(todo)) return;
-    fill_te4(s_te);
-    if (!todo) return;
-    gcm_wave_pass<MODE>(a, s_te, p, ks_id, lane);
+    if constexpr (MODE == kGcmFix) {
+        const int act = gcm_fix_todo(a, p, ks_id);
+        if (!__syncthreads_or(act != kGcmFixNone)) return;
+        fill_te4(s_te);
+        if (act == kGcmFixNone) return;
+        gcm_wave_fix(a, s_te, p, ks_id, lane, act);
+    } else {
+        constexpr int kList = MODE == kGcmOpen ? kGcmVerify : MODE; // the open pass's work list is verify's
+        const bool todo = gcm_wave_todo<kList>(a, p, ks_id);
+        if (!__syncthreads_or(todo)) return;
+        fill_te4(s_te);
+        if (!todo) return;
+        if constexpr (MODE == kGcmOpen) gcm_wave_open(a, s_te, p, ks_id, lane);
+        else gcm_wave_pass<MODE>(a, s_te, p, ks_id, lane);
+    }
 }
 
 // ============================================================== maintenance
@@ -5711,12 +5964,15 @@ hipError_t launch_gcm_aead_wave(const GcmBatchWave &g, hipStream_t s) {
     return hipGetLastError();
 }
 hipError_t launch_gcm(const BundleArgs &a, int mode, hipStream_t s) {
-    const bool wave = a.gcm_route ? a.gcm_route == kGcmRouteWave : a.n <= kGcmWaveMax;
+    const int32_t route = a.gcm_route & kGcmRouteMask;
+    const bool wave = route ? route == kGcmRouteWave : a.n <= kGcmWaveMax;
     if (wave) { // a wave per packet (the per-packet paths' small bundles)
         const uint32_t per = (uint32_t)(kGcmWaveBlock / 64);
         const dim3 grid((a.n + per - 1) / per), block(kGcmWaveBlock);
         if (mode == kGcmVerify) hipLaunchKernelGGL(k_gcm_wave<kGcmVerify>, grid, block, 0, s, a);
         else if (mode == kGcmDecipher) hipLaunchKernelGGL(k_gcm_wave<kGcmDecipher>, grid, block, 0, s, a);
+        else if (mode == kGcmOpen) hipLaunchKernelGGL(k_gcm_wave<kGcmOpen>, grid, block, 0, s, a);
+        else if (mode == kGcmFix) hipLaunchKernelGGL(k_gcm_wave<kGcmFix>, grid, block, 0, s, a);
         else hipLaunchKernelGGL(k_gcm_wave<kGcmSeal>, grid, block, 0, s, a);
         return hipGetLastError();
     }
@@ -5724,6 +5980,8 @@ hipError_t launch_gcm(const BundleArgs &a, int mode, hipStream_t s) {
     const dim3 grid((a.n + b - 1) / b), block(b);
     if (mode == kGcmVerify) hipLaunchKernelGGL(k_gcm<kGcmVerify>, grid, block, 0, s, a);
     else if (mode == kGcmDecipher) hipLaunchKernelGGL(k_gcm<kGcmDecipher>, grid, block, 0, s, a);
+    else if (mode == kGcmOpen) hipLaunchKernelGGL(k_gcm<kGcmOpen>, grid, block, 0, s, a);
+    else if (mode == kGcmFix) hipLaunchKernelGGL(k_gcm<kGcmFix>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(k_gcm<kGcmSeal>, grid, block, 0, s, a);
     return hipGetLastError();
 }

@@ -140,6 +140,12 @@ constexpr uint32_t kSpecDid = 1u;  // decrypted in place under the ROC guess
 constexpr uint32_t kSpecAes = 2u;  // AES-128-CM key set of the fused path (not k_ext's)
 constexpr uint32_t kSpecRtp = 4u;  // SRTP (else SRTCP)
 constexpr uint32_t kSpecSkip = 8u; // SRTP packet flagged DISCARD / SILENCE: not deciphered
+// k_gcm<kGcmOpen> (a packet of an AES-GCM key set): its tag matched under the
+// ROC guess and it was deciphered in the same trip.  Bits 16-31 of the word
+// then hold the length the packet came with (every open-pass packet's do).
+// Never kSpecDid: k_unprotect_fix would "repair" the packet with AES-CM keystream.
+constexpr uint32_t kSpecGcm = 16u;
+constexpr uint32_t kSpecLowMask = 0xFu; // k_unprotect's own bits
 constexpr uint32_t kRecIdxMask = 0x0FFFFFFFu;
 constexpr int32_t kHdrThrow = (int32_t)0x80000000; // getHeaderLength would throw
 
@@ -173,6 +179,9 @@ constexpr int kCtrOverflow = 18;     // packets refused a new context (table ful
 constexpr int kCtrChainStall = 19;   // walk tiles that gave up waiting on a long chain's look-back
                                      // (their chain is then walked by the fix-up; never expected)
 constexpr int kCtrLongWalked = 20;   // records walk_long walked one at a time (they broke the speculation)
+constexpr int kCtrGcmOpened = 21;   // GCM packets deciphered with their tag check (k_gcm<kGcmOpen>)
+constexpr int kCtrGcmRestored = 22; // ... of those, put back as ciphertext after the walk (k_gcm<kGcmFix>)
+constexpr int kCtrGcmLate = 23;     // GCM packets deciphered after the walk on the one-pass route
 constexpr int kCtrStride = 32;       // u64 words per replica (one 256-B line)
 
 // internal walk statuses (beyond SRTP_STATUS_*)

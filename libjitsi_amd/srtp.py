@@ -273,6 +273,14 @@ class SRTPEngine:
         N.check(N.lib().srtp_engine_stats(self.h, C.byref(st)), self.h, "stats")
         return st.as_dict()
 
+    def gcm_stats(self) -> dict:
+        """srtp_engine_gcm_stats: AES-GCM packets deciphered with their tag
+        check (opened), of those put back as ciphertext after the walk
+        (restored), and deciphered after the walk (late)."""
+        st = N.GcmStats()
+        N.check(N.lib().srtp_engine_gcm_stats(self.h, C.byref(st)), self.h, "gcm_stats")
+        return st.as_dict()
+
     # -- control plane used by SRTPContextFactory / SRTPTransformer ----------
     def _factory_create(self, sender, key, salt, klen, slen, srtp, srtcp) -> int:
         fid = C.c_int32()
@@ -463,6 +471,12 @@ class SRTPDispatcher:
     def stats(self) -> dict:
         st = N.Stats()
         self._chk(N.lib().srtp_dispatch_stats(self.h, C.byref(st)), "stats")
+        return st.as_dict()
+
+    def gcm_stats(self) -> dict:
+        """srtp_dispatch_gcm_stats: SRTPEngine.gcm_stats summed over the shards."""
+        st = N.GcmStats()
+        self._chk(N.lib().srtp_dispatch_gcm_stats(self.h, C.byref(st)), "gcm_stats")
         return st.as_dict()
 
     def enable_aead(self, on: bool = True) -> None:
