@@ -200,6 +200,85 @@ int srtp_transform_host(srtp_engine *e, int32_t reverse, const int32_t *tids, in
                         uint8_t *seg, size_t seg_bytes, const uint32_t *off, uint32_t *len,
                         const uint32_t *cap, const uint32_t *flags, int32_t *status, uint32_t n);
 
+/* Fan-out: one packet to many peers, expanded on the device.  A bridge receives
+ * a packet once and sends it to N peers, each under its own keys -- the
+ * reference's OutputDataStreamImpl.doWrite hands the same buf, off, len to every
+ * stream (rtp/translator/OutputDataStreamImpl.java:171-243), and each stream's
+ * connector copies it and runs its own SRTPTransformer.transform.  Here m
+ * source packets (a bundle's layout: src_seg, src_off, src_len, src_cap) and n
+ * destination entries, entry j = (src_idx[j], tids[j] or tid, region off[j] /
+ * cap[j] of seg): entry j becomes a copy of source src_idx[j] (k_fanout, in
+ * device memory) and the n entries are then protected as one bundle -- exactly
+ * as if each had been a host-made copy of its source submitted in that order
+ * to srtp_transform_device(reverse = 0): every profile, per-context order
+ * within the bundle, abort-on-throw and the counters are that call's.  len is
+ * output only.
+ *
+ * An entry is skipped -- nothing copied, its region untouched, len[j] = 0,
+ * status SRTP_STATUS_SKIPPED -- when src_idx[j] is not in [0, m), when
+ * src_status[src_idx[j]] is not SRTP_STATUS_OK (the reference's null element: a
+ * packet reverseTransform dropped is never written by the translator;
+ * src_status NULL: every source is OK) or when flags[j] carries
+ * SRTP_PKT_FLAG_SKIP.  Otherwise len[j] = src_len[src_idx[j]] and
+ * min(src_len, src_cap, cap[j]) bytes rounded up to 16 are copied; a source
+ * longer than cap[j] ends SRTP_STATUS_DROP_INVALID, a region too small for the
+ * trailer SRTP_STATUS_ERR_CAPACITY, by the existing rules (srtp_fanout_job is
+ * the rule, on the host).  Nothing of the packet is rewritten per destination
+ * (SSRC, sequence number, payload type): the reference's translator rewrites
+ * none.
+ *
+ * srtp_fanout_device: every array is a device pointer, the call asynchronous on
+ * `stream` like srtp_transform_device, under the engine's lock while it
+ * enqueues.  src_len and src_status are read on the device, so the len and
+ * status arrays of a preceding srtp_transform_device(reverse = 1) on the same
+ * stream feed them without a synchronise: a received bundle is forwarded with
+ * no host round trip.  The caller guarantees for both segments what
+ * srtp_transform_device asks of its regions, and that the two segments do not
+ * overlap; an out-of-range src_idx is not the caller's guarantee (skipped,
+ * above).  m = 0 with n > 0 is SRTP_EINVAL.
+ *
+ * srtp_fanout_host: host pointers.  Checks both region tables as
+ * srtp_transform_host does, src_idx[j] in [0, m) and m >= 1 (else SRTP_EINVAL,
+ * nothing launched), copies only the source segment and the small arrays to
+ * the device, expands and protects there, copies the destination segment, len
+ * and status back and synchronises.  The host destination segment is OUTPUT
+ * ONLY: after the call the bytes [off[j], off[j] + len[j]) of the entries with
+ * SRTP_STATUS_OK are defined, every other byte of it is unspecified (whatever
+ * it held before is lost).
+ *
+ * n = 0 is SRTP_OK with nothing launched; a NULL engine SRTP_EINVAL before any
+ * device call. */
+int srtp_fanout_device(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
+                       const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status,
+                       uint32_t m, const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                       const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                       int32_t *status, uint32_t n, void *stream);
+int srtp_fanout_host(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_bytes, const uint32_t *src_off,
+                     const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status,
+                     uint32_t m, const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                     size_t seg_bytes, const uint32_t *off, uint32_t *len, const uint32_t *cap,
+                     const uint32_t *flags, int32_t *status, uint32_t n);
+/* Cumulative since engine creation: fan-out calls that were enqueued, their
+ * sources (m) and destination entries (n), the entries skipped for their index
+ * or their source's status (not those the caller flagged), and the source bytes
+ * srtp_fanout_host copied host-to-device. */
+typedef struct {
+    uint64_t calls, sources, destinations, skipped, src_bytes_h2d;
+} srtp_fanout_stats;
+int srtp_engine_fanout_stats(srtp_engine *e, srtp_fanout_stats *out);
+/* The rule of one destination entry (host only; fanout_job.h, the text k_fanout
+ * compiles): the bytes to copy (a multiple of 16, never past either region
+ * rounded up to 16), the entry's length and flags word, and by_source = 1 when
+ * it is skipped for its index or its source's status.  src_len, src_cap and
+ * src_status matter only for an index in [0, m). */
+typedef struct {
+    int32_t copy_bytes, len_out;
+    uint32_t flags_out;
+    int32_t by_source;
+} srtp_fanout_plan;
+int srtp_fanout_job(int32_t src_idx, int32_t m, int32_t src_len, int32_t src_cap, int32_t src_status,
+                    int32_t dst_cap, uint32_t flags, srtp_fanout_plan *out);
+
 /* The engine's own non-blocking stream, created with the engine so that each
  * engine gets a hardware queue of its own (streams created later may share
  * one, which serialises them): srtp_transform_host and the pipeline run their

@@ -88,6 +88,7 @@ EXPORTED = [
     "srtp_engine_gcm_stats", "srtp_dispatch_gcm_stats", "srtp_gcm_open_lane_min", "srtp_gcm_open_wave_min",
     "srtp_gcm_open_wave_max",
     "srtp_gcm_spec_ok", "srtp_gcm_fix_action",
+    "srtp_fanout_device", "srtp_fanout_host", "srtp_engine_fanout_stats", "srtp_fanout_job",
 ]
 STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 
@@ -95,7 +96,7 @@ STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 # Sources that decide what the crypto kernels execute: the key that ties
 # committed PMC counters (profiles/pmc_traffic.json) to the build they measured.
 KERNEL_SOURCES = ["srtp_kernels.hip", "aes_rounds_asm.inc", "srtp_kernels.h", "srtp_types.h", "engine.cpp",
-                  "gcm_job.h"]
+                  "gcm_job.h", "fanout_job.h"]
 
 
 def kernel_source_sha16() -> str:
@@ -172,6 +173,20 @@ class GcmStats(C.Structure):
 
     def as_dict(self) -> dict:
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class FanoutStats(C.Structure):
+    """srtp_fanout_stats (include/srtp_mi355x.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "sources", "destinations", "skipped", "src_bytes_h2d")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class FanoutPlan(C.Structure):
+    """srtp_fanout_plan (include/srtp_mi355x.h)"""
+    _fields_ = [("copy_bytes", C.c_int32), ("len_out", C.c_int32), ("flags_out", C.c_uint32),
+                ("by_source", C.c_int32)]
 
 
 DTLS_AEAD = 0x1
@@ -313,6 +328,11 @@ def lib() -> C.CDLL:
     L.srtp_gcm_spec_ok.restype = i32
     L.srtp_gcm_fix_action.argtypes = [i32, i32, i32, i32, u32, u32]
     L.srtp_gcm_fix_action.restype = i32
+    L.srtp_fanout_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, i32, vp, vp, vp, vp, vp, vp, u32, vp]
+    L.srtp_fanout_host.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, u32, vp, vp, i32, vp, C.c_size_t, vp, vp,
+                                   vp, vp, vp, u32]
+    L.srtp_engine_fanout_stats.argtypes = [vp, C.POINTER(FanoutStats)]
+    L.srtp_fanout_job.argtypes = [i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutPlan)]
     L.srtp_trailer_room.argtypes = [i32]
     L.srtp_trailer_room.restype = i32
     L.srtp_engine_trailer_room.argtypes = [vp]

@@ -18,6 +18,7 @@
 #include <string.h>
 
 #include "../../include/srtp_mi355x.h"
+#include "fanout_job.h"
 #include "gcm_job.h"
 #include "host_crypto.h"
 #include "srtp_kernels.h"
@@ -104,6 +105,19 @@ struct srtp_engine {
     uint32_t h_n = 0;
     uint32_t *h_off = nullptr, *h_len = nullptr, *h_cap = nullptr, *h_flags = nullptr;
     int32_t *h_status = nullptr, *h_tids = nullptr;
+
+    // fan-out (srtp_fanout_*): the engine-owned flags words of the destination
+    // entries (k_fanout writes them, the protect chain reads them), the count of
+    // entries skipped for their source, and srtp_fanout_host's source staging
+    uint32_t *fan_flags = nullptr;
+    uint32_t fan_n = 0;
+    unsigned long long *d_fan_skipped = nullptr;
+    uint8_t *hs_seg = nullptr;
+    size_t hs_seg_bytes = 0;
+    uint32_t hs_m = 0, hs_n = 0;
+    uint32_t *hs_off = nullptr, *hs_len = nullptr, *hs_cap = nullptr;
+    int32_t *hs_status = nullptr, *hs_idx = nullptr;
+    uint64_t fan_calls = 0, fan_sources = 0, fan_destinations = 0, fan_src_bytes = 0;
 
     // optional per-stage timing (HIP events on the bundle stream)
     bool timing = false;
@@ -594,7 +608,8 @@ void srtp_engine_destroy(srtp_engine *e) {
     for (auto ev : e->event_pool) (void)hipEventDestroy(ev);
     void *ptrs[] = {e->d_keysets, e->d_extkeys, e->d_tfkeys, e->d_skkeys, e->d_gcmkeys, e->d_gcmpow, e->d_factories, e->d_transformers, e->d_ctx_keys, e->d_ctx,
                     e->d_far, e->e_min, e->ctl, e->d_count, e->d_counters, e->h_seg, e->h_off, e->h_len,
-                    e->h_cap, e->h_flags, e->h_status, e->h_tids};
+                    e->h_cap, e->h_flags, e->h_status, e->h_tids, e->fan_flags, e->d_fan_skipped, e->hs_seg,
+                    e->hs_off, e->hs_len, e->hs_cap, e->hs_status, e->hs_idx};
     for (void *p : ptrs) dfree(p);
     if (e->ev_last) (void)hipEventDestroy(e->ev_last);
     if (e->ev_dev) (void)hipEventDestroy(e->ev_dev);
@@ -1015,6 +1030,39 @@ static int validate_regions(srtp_engine *e, const uint32_t *off, const uint32_t 
     return SRTP_OK;
 }
 
+// The device staging of a host bundle (srtp_transform_host, srtp_fanout_host's
+// destination side): a segment of seg_bytes and the arrays of n packets.
+static int ensure_host_staging(srtp_engine *e, size_t seg_bytes, uint32_t n) {
+    size_t need = (seg_bytes + 15) & ~(size_t)15;
+    if ((need > e->h_seg_bytes || n > e->h_n) && e->have_last) {
+        // the staging buffers may still be in use by an enqueued bundle
+        int qrc = quiesce(e);
+        if (qrc != SRTP_OK) return qrc;
+    }
+    if (need > e->h_seg_bytes) {
+        dfree(e->h_seg);
+        e->h_seg = nullptr;
+        e->h_seg_bytes = 0;
+        HIPCHK(e, hipMalloc(&e->h_seg, need));
+        e->h_seg_bytes = need;
+    }
+    if (n > e->h_n) {
+        void *ptrs[] = {e->h_off, e->h_len, e->h_cap, e->h_flags, e->h_status, e->h_tids};
+        for (void *p : ptrs) dfree(p);
+        e->h_off = e->h_len = e->h_cap = e->h_flags = nullptr;
+        e->h_status = e->h_tids = nullptr;
+        e->h_n = 0;
+        HIPCHK(e, dalloc(&e->h_off, n));
+        HIPCHK(e, dalloc(&e->h_len, n));
+        HIPCHK(e, dalloc(&e->h_cap, n));
+        HIPCHK(e, dalloc(&e->h_flags, n));
+        HIPCHK(e, dalloc(&e->h_status, n));
+        HIPCHK(e, dalloc(&e->h_tids, n));
+        e->h_n = n;
+    }
+    return SRTP_OK;
+}
+
 int srtp_transform_host(srtp_engine *e, int32_t reverse, const int32_t *tids, int32_t tid,
                         uint8_t *seg, size_t seg_bytes, const uint32_t *off, uint32_t *len,
                         const uint32_t *cap, const uint32_t *flags, int32_t *status, uint32_t n) {
@@ -1026,29 +1074,8 @@ int srtp_transform_host(srtp_engine *e, int32_t reverse, const int32_t *tids, in
     if (vr != SRTP_OK) return vr;
     GUARD(e);
     hipStream_t s = e->stream;
-    size_t need = (seg_bytes + 15) & ~(size_t)15;
-    if ((need > e->h_seg_bytes || n > e->h_n) && e->have_last) {
-        // the staging buffers may still be in use by an enqueued bundle
-        int qrc = quiesce(e);
-        if (qrc != SRTP_OK) return qrc;
-    }
-    if (need > e->h_seg_bytes) {
-        dfree(e->h_seg);
-        e->h_seg = nullptr;
-        HIPCHK(e, hipMalloc(&e->h_seg, need));
-        e->h_seg_bytes = need;
-    }
-    if (n > e->h_n) {
-        void *ptrs[] = {e->h_off, e->h_len, e->h_cap, e->h_flags, e->h_status, e->h_tids};
-        for (void *p : ptrs) dfree(p);
-        HIPCHK(e, dalloc(&e->h_off, n));
-        HIPCHK(e, dalloc(&e->h_len, n));
-        HIPCHK(e, dalloc(&e->h_cap, n));
-        HIPCHK(e, dalloc(&e->h_flags, n));
-        HIPCHK(e, dalloc(&e->h_status, n));
-        HIPCHK(e, dalloc(&e->h_tids, n));
-        e->h_n = n;
-    }
+    int hrc = ensure_host_staging(e, seg_bytes, n);
+    if (hrc != SRTP_OK) return hrc;
     HIPCHK(e, hipMemcpyAsync(e->h_seg, seg, seg_bytes, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(e->h_off, off, n * 4ull, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(e->h_len, len, n * 4ull, hipMemcpyHostToDevice, s));
@@ -1066,6 +1093,177 @@ int srtp_transform_host(srtp_engine *e, int32_t reverse, const int32_t *tids, in
 }
 
 void *srtp_engine_stream(srtp_engine *e) { return e ? (void *)e->stream : nullptr; }
+
+// ------------------------------------------------------------------ fan-out
+// k_fanout in front of the protect chain, both on `s`.  The flags words the
+// chain reads are the engine's (fan_flags), so the expansion waits, like a
+// bundle, for the previous bundle of another stream.
+static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
+                         const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status, uint32_t m,
+                         const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                         const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                         int32_t *status, uint32_t n, hipStream_t s, bool dev_event) {
+    if (!src_seg || !src_off || !src_len || !src_cap || !src_idx || !seg || !off || !len || !cap || !status)
+        return fail(e, SRTP_EINVAL, "null buffer");
+    if (m == 0) return fail(e, SRTP_EINVAL, "fan-out without a source");
+    if (n > kRecIdxMask || m > kRecIdxMask) return fail(e, SRTP_EINVAL, "bundle too large");
+    if (!tids && (tid < 0 || (size_t)tid >= e->transformers.size()))
+        return fail(e, SRTP_EINVAL, "bad transformer id");
+    int rc = ensure_scratch(e, n);
+    if (rc != SRTP_OK) return rc;
+    if (n > e->fan_n) {
+        if (e->have_last) { // the old flags words may still be read by an enqueued bundle
+            rc = quiesce(e);
+            if (rc != SRTP_OK) return rc;
+        }
+        dfree(e->fan_flags);
+        e->fan_flags = nullptr;
+        e->fan_n = 0;
+        const uint32_t want = std::max<uint32_t>(n, 1024);
+        HIPCHK(e, dalloc(&e->fan_flags, want));
+        e->fan_n = want;
+    }
+    if (!e->d_fan_skipped) {
+        HIPCHK(e, dalloc(&e->d_fan_skipped, 1));
+        HIPCHK(e, hipMemset(e->d_fan_skipped, 0, sizeof(unsigned long long)));
+    }
+    if (e->have_last && e->last_stream != s) HIPCHK(e, hipStreamWaitEvent(s, last_event(e), 0));
+    FanoutArgs f{};
+    f.src_seg = src_seg; f.src_off = src_off; f.src_len = src_len; f.src_cap = src_cap;
+    f.src_status = src_status; f.m = m; f.src_idx = src_idx;
+    f.seg = seg; f.off = off; f.cap = cap; f.flags = flags; f.len = len;
+    f.flags_out = e->fan_flags;
+    f.skipped = e->d_fan_skipped;
+    f.n = n;
+    HIPCHK(e, launch_fanout(f, s));
+    rc = transform_locked(e, 0, tids, tid, seg, off, len, cap, e->fan_flags, status, n, s, -1, dev_event);
+    if (rc != SRTP_OK) return rc;
+    e->fan_calls++;
+    e->fan_sources += m;
+    e->fan_destinations += n;
+    return SRTP_OK;
+}
+
+int srtp_fanout_device(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off, const uint32_t *src_len,
+                       const uint32_t *src_cap, const int32_t *src_status, uint32_t m, const int32_t *src_idx,
+                       const int32_t *tids, int32_t tid, uint8_t *seg, const uint32_t *off, uint32_t *len,
+                       const uint32_t *cap, const uint32_t *flags, int32_t *status, uint32_t n, void *stream) {
+    if (!e) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (n == 0) return SRTP_OK;
+    GUARD(e);
+    return fanout_locked(e, src_seg, src_off, src_len, src_cap, src_status, m, src_idx, tids, tid, seg, off, len,
+                         cap, flags, status, n, (hipStream_t)stream, true);
+}
+
+int srtp_fanout_host(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_bytes, const uint32_t *src_off,
+                     const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status, uint32_t m,
+                     const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg, size_t seg_bytes,
+                     const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                     int32_t *status, uint32_t n) {
+    if (!e) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (n == 0) return SRTP_OK;
+    if (!src_seg || !src_off || !src_len || !src_cap || !src_idx || !seg || !off || !len || !cap || !status)
+        return fail(e, SRTP_EINVAL, "null buffer");
+    if (m == 0) return fail(e, SRTP_EINVAL, "fan-out without a source");
+    if (n > kRecIdxMask || m > kRecIdxMask) return fail(e, SRTP_EINVAL, "bundle too large");
+    int vr = validate_regions(e, src_off, src_cap, m, src_seg_bytes);
+    if (vr != SRTP_OK) return vr;
+    vr = validate_regions(e, off, cap, n, seg_bytes);
+    if (vr != SRTP_OK) return vr;
+    for (uint32_t j = 0; j < n; j++)
+        if (src_idx[j] < 0 || (uint32_t)src_idx[j] >= m) return fail(e, SRTP_EINVAL, "src_idx[j] names no source");
+    if (!tids && (tid < 0 || (size_t)tid >= e->transformers.size()))
+        return fail(e, SRTP_EINVAL, "bad transformer id");
+    GUARD(e);
+    hipStream_t s = e->stream;
+    int rc = ensure_host_staging(e, seg_bytes, n);
+    if (rc != SRTP_OK) return rc;
+    const size_t need = (src_seg_bytes + 15) & ~(size_t)15;
+    if ((need > e->hs_seg_bytes || m > e->hs_m || n > e->hs_n) && e->have_last) {
+        rc = quiesce(e); // the source staging may still be read by an enqueued fan-out
+        if (rc != SRTP_OK) return rc;
+    }
+    if (need > e->hs_seg_bytes) {
+        dfree(e->hs_seg);
+        e->hs_seg = nullptr;
+        e->hs_seg_bytes = 0;
+        HIPCHK(e, hipMalloc(&e->hs_seg, need));
+        e->hs_seg_bytes = need;
+    }
+    if (m > e->hs_m) {
+        void *ptrs[] = {e->hs_off, e->hs_len, e->hs_cap, e->hs_status};
+        for (void *p : ptrs) dfree(p);
+        e->hs_off = e->hs_len = e->hs_cap = nullptr;
+        e->hs_status = nullptr;
+        e->hs_m = 0;
+        HIPCHK(e, dalloc(&e->hs_off, m));
+        HIPCHK(e, dalloc(&e->hs_len, m));
+        HIPCHK(e, dalloc(&e->hs_cap, m));
+        HIPCHK(e, dalloc(&e->hs_status, m));
+        e->hs_m = m;
+    }
+    if (n > e->hs_n) {
+        dfree(e->hs_idx);
+        e->hs_idx = nullptr;
+        e->hs_n = 0;
+        HIPCHK(e, dalloc(&e->hs_idx, n));
+        e->hs_n = n;
+    }
+    // only the source segment and the small arrays cross to the device
+    HIPCHK(e, hipMemcpyAsync(e->hs_seg, src_seg, src_seg_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->hs_off, src_off, m * 4ull, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->hs_len, src_len, m * 4ull, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->hs_cap, src_cap, m * 4ull, hipMemcpyHostToDevice, s));
+    if (src_status) HIPCHK(e, hipMemcpyAsync(e->hs_status, src_status, m * 4ull, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->hs_idx, src_idx, n * 4ull, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->h_off, off, n * 4ull, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->h_cap, cap, n * 4ull, hipMemcpyHostToDevice, s));
+    if (flags) HIPCHK(e, hipMemcpyAsync(e->h_flags, flags, n * 4ull, hipMemcpyHostToDevice, s));
+    if (tids) HIPCHK(e, hipMemcpyAsync(e->h_tids, tids, n * 4ull, hipMemcpyHostToDevice, s));
+    rc = fanout_locked(e, e->hs_seg, e->hs_off, e->hs_len, e->hs_cap, src_status ? e->hs_status : nullptr, m,
+                       e->hs_idx, tids ? e->h_tids : nullptr, tid, e->h_seg, e->h_off, e->h_len, e->h_cap,
+                       flags ? e->h_flags : nullptr, e->h_status, n, s, false);
+    if (rc != SRTP_OK) return rc;
+    e->fan_src_bytes += src_seg_bytes;
+    HIPCHK(e, hipMemcpyAsync(seg, e->h_seg, seg_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(len, e->h_len, n * 4ull, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(status, e->h_status, n * 4ull, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    return SRTP_OK;
+}
+
+int srtp_engine_fanout_stats(srtp_engine *e, srtp_fanout_stats *out) {
+    if (!e || !out) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    memset(out, 0, sizeof *out);
+    out->calls = e->fan_calls;
+    out->sources = e->fan_sources;
+    out->destinations = e->fan_destinations;
+    out->src_bytes_h2d = e->fan_src_bytes;
+    if (!e->d_fan_skipped) return SRTP_OK; // no fan-out yet
+    GUARD(e);
+    int rc = quiesce(e);
+    if (rc != SRTP_OK) return rc;
+    unsigned long long sk = 0;
+    HIPCHK(e, hipMemcpy(&sk, e->d_fan_skipped, sizeof sk, hipMemcpyDeviceToHost));
+    out->skipped = sk;
+    return SRTP_OK;
+}
+
+int srtp_fanout_job(int32_t src_idx, int32_t m, int32_t src_len, int32_t src_cap, int32_t src_status,
+                    int32_t dst_cap, uint32_t flags, srtp_fanout_plan *out) {
+    if (!out) return SRTP_EINVAL;
+    static_assert(SRTP_PKT_FLAG_SKIP == kFanFlagSkip && SRTP_STATUS_OK == kFanStatusOk,
+                  "fanout_job.h restates these constants");
+    const FanoutJob j = fanout_job(src_idx, m, src_len, src_cap, src_status, dst_cap, flags);
+    out->copy_bytes = j.copy_bytes;
+    out->len_out = j.len_out;
+    out->flags_out = j.flags_out;
+    out->by_source = j.by_source;
+    return SRTP_OK;
+}
 
 int srtp_engine_sync(srtp_engine *e, void *stream) {
     if (!e) return SRTP_EINVAL;

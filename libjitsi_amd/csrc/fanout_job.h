@@ -1,0 +1,81 @@
+// fanout_job.h -- what one destination entry of a fan-out (srtp_fanout_device /
+// _host: m source packets, n entries of (source index, transformer, destination
+// region)) gets before the protect chain sees it: skipped, or a copy of its
+// source of so many bytes and the source's length.  One plain function that the
+// host compiles (srtp_fanout_job, tools/fanout_check.cpp under AddressSanitizer
+// + UBSan) and k_fanout compiles as it stands (no HIP type, no pointer): the
+// kernel copies exactly copy_bytes, and no byte count leaves here before it is
+// shown to lie inside both regions.  All arithmetic is signed int.
+//
+// The rules:
+//   skipped   src_idx < 0 or >= m; the source's status is not OK (the reference's
+//             null element: a packet reverseTransform dropped is never written
+//             by the translator); the caller's flags carry SKIP.  Nothing is
+//             copied, flags_out = caller's | SKIP, len_out = 0: the entry ends
+//             SRTP_STATUS_SKIPPED.  by_source tells the first two reasons from
+//             the third (srtp_fanout_stats.skipped).
+//   otherwise len_out = src_len and copy_bytes = min(src_len, src_cap, dst_cap)
+//             rounded up to 16: never past dst_cap rounded up to 16 nor past
+//             src_cap rounded up to 16, which is what a region owns
+//             (srtp_transform_device).  A source longer than dst_cap keeps its
+//             length, and the parse answers DROP_INVALID (len > cap,
+//             RawPacket.isInvalid) as for a host-made copy; a region too small
+//             for the trailer ends ERR_CAPACITY there.  A length or capacity
+//             that is negative as an int (above 2^31 as the uint32 it came from)
+//             copies nothing; one above 65535 (no region is larger: the
+//             kernels' 16-bit length fields) counts as 65535.
+// Fan-out decides nothing else about a packet: the rest is the protect chain's.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define SRTP_FANOUT_HD __host__ __device__
+#else
+#define SRTP_FANOUT_HD
+#endif
+
+namespace srtp {
+
+constexpr uint32_t kFanFlagSkip = 0x80000000u; // SRTP_PKT_FLAG_SKIP (this header stands alone)
+constexpr int kFanStatusOk = 0;                // SRTP_STATUS_OK
+constexpr int kFanMaxRegion = 65535;           // validate_regions: cap <= 65535
+
+struct FanoutJob {
+    int32_t copy_bytes; // a multiple of 16; 0: nothing to copy
+    int32_t len_out;    // the entry's length (the source's, as the uint32 it was)
+    uint32_t flags_out; // the entry's flags word
+    int32_t by_source;  // 1: skipped for its index or its source's status
+};
+
+SRTP_FANOUT_HD inline int fanout_clamp(int v) { return v < 0 ? 0 : v > kFanMaxRegion ? kFanMaxRegion : v; }
+
+// src_len, src_cap, src_status: the source's, read only when src_idx is in
+// range (any value otherwise); src_status 0 where the caller gave no statuses.
+SRTP_FANOUT_HD inline FanoutJob fanout_job(int src_idx, int m, int src_len, int src_cap, int src_status,
+                                           int dst_cap, uint32_t caller_flags) {
+    FanoutJob j;
+    j.copy_bytes = 0;
+    j.len_out = 0;
+    j.flags_out = caller_flags | kFanFlagSkip;
+    j.by_source = 0;
+    if (src_idx < 0 || src_idx >= m || src_status != kFanStatusOk) {
+        j.by_source = 1;
+        return j;
+    }
+    if (caller_flags & kFanFlagSkip) return j;
+    j.flags_out = caller_flags;
+    j.len_out = src_len;
+    if (src_len < 0 || src_cap < 0 || dst_cap < 0) return j; // no such region: the parse refuses the entry
+    const int sc = fanout_clamp(src_cap), dc = fanout_clamp(dst_cap);
+    int c = fanout_clamp(src_len);
+    if (c > sc) c = sc;
+    if (c > dc) c = dc;
+    const int copy = (c + 15) & ~15; // c <= 65535: at most 65536
+    // The proof, once more, on what is about to be handed out.  It cannot fail
+    // by the lines above; should an edit break one, nothing is copied.
+    const bool ok = copy >= 0 && (copy & 15) == 0 && copy <= ((sc + 15) & ~15) && copy <= ((dc + 15) & ~15);
+    j.copy_bytes = ok ? copy : 0;
+    return j;
+}
+
+} // namespace srtp

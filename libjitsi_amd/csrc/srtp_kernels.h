@@ -207,6 +207,29 @@ hipError_t launch_small(const BundleArgs &a, hipStream_t s);
 // an interleaved registered host bundle)
 hipError_t launch_move_regions(bool to_device, uint8_t *dseg, const uint32_t *doff, const uint32_t *cap,
                                uint8_t *host, const uint32_t *src, uint32_t n, hipStream_t s);
+// srtp_fanout_device: m source packets expanded to n destination entries in
+// device memory, in front of the protect chain (k_fanout).  Entry j takes
+// fanout_job's answer (fanout_job.h) for source src_idx[j]: len[j] and the
+// engine's flags word flags_out[j] are written, and the job's copy_bytes go
+// from src_seg + src_off[src_idx[j]] to seg + off[j].  Whether an entry has
+// work is decided from the index, m, the status word and the flags before any
+// pointer into either segment is formed.  skipped += the entries skipped for
+// their index or their source's status.
+struct FanoutArgs {
+    const uint8_t *src_seg;
+    const uint32_t *src_off, *src_len, *src_cap;
+    const int32_t *src_status; // may be null: every source OK
+    uint32_t m;                // <= INT32_MAX
+    const int32_t *src_idx;    // [n]
+    uint8_t *seg;
+    const uint32_t *off, *cap; // [n]
+    const uint32_t *flags;     // [n] the caller's, may be null
+    uint32_t *len;             // [n] out
+    uint32_t *flags_out;       // [n] out
+    unsigned long long *skipped;
+    uint32_t n;
+};
+hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s);
 // unprotect: statuses/lengths out; undo/redo the rare speculation misses (after the walk)
 hipError_t launch_unprotect_fix(const BundleArgs &a, hipStream_t s);
 // AES-F8 packets after the final statuses: protect (F8 + HMAC + trailer) or

@@ -63,6 +63,7 @@
 
 
 #include "../../include/srtp_mi355x.h"
+#include "fanout_job.h"
 #include "gcm_job.h"
 #include "srtp_kernels.h"
 
@@ -7091,6 +7092,80 @@ hipError_t launch_move_regions(bool to_device, uint8_t *dseg, const uint32_t *do
         hipLaunchKernelGGL(k_move_regions<true>, dim3(wgs), dim3(kGatherBlock), 0, s, dseg, doff, cap, host, src, n);
     else
         hipLaunchKernelGGL(k_move_regions<false>, dim3(wgs), dim3(kGatherBlock), 0, s, dseg, doff, cap, host, src, n);
+    return hipGetLastError();
+}
+
+// ================================================================== fan-out
+// One packet to many peers (srtp_fanout_device): entry j of the destination
+// bundle becomes a copy of source src_idx[j], in HBM, in front of the protect
+// chain -- what OutputDataStreamImpl.doWrite does by handing the same buffer
+// to every stream (rtp/translator/OutputDataStreamImpl.java:171-243).  A wave
+// takes two entries at a time and moves them k_move_regions' way: 16 B per lane
+// per instruction, every load of a trip issued before its stores.  fanout_job
+// (fanout_job.h) says whether an entry has work and how many bytes; it is asked
+// with the index, m, the source's status, lengths and the flags alone, and
+// only an entry with bytes to copy forms a pointer into either segment.  In a
+// source-major bundle the two entries of a wave, and the waves around it,
+// read the same source: its re-reads come from the L2.
+struct FanEntry {
+    FanoutJob job;
+    uint32_t src_at; // the source region's offset (copy_bytes > 0 only)
+};
+__device__ __forceinline__ FanEntry fan_entry(const FanoutArgs &f, uint32_t j) {
+    const int si = f.src_idx[j];
+    const uint32_t fl = f.flags ? f.flags[j] : 0u;
+    const bool in = si >= 0 && si < (int)f.m;
+    const int st = in && f.src_status ? f.src_status[si] : 0;
+    const int sl = in ? (int)f.src_len[si] : 0, sc = in ? (int)f.src_cap[si] : 0;
+    FanEntry e;
+    e.job = fanout_job(si, (int)f.m, sl, sc, st, (int)f.cap[j], fl);
+    e.src_at = e.job.copy_bytes > 0 ? f.src_off[si] : 0u;
+    return e;
+}
+
+__global__ __launch_bounds__(kGatherBlock) void k_fanout(FanoutArgs f) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t waves = gridDim.x * (kGatherBlock / 64);
+    for (uint32_t j = 2u * (blockIdx.x * (kGatherBlock / 64) + (threadIdx.x >> 6)); j < f.n; j += 2u * waves) {
+        const bool two = j + 1u < f.n;
+        const FanEntry ea = fan_entry(f, j), eb = fan_entry(f, two ? j + 1u : j);
+        if (lane == 0u) {
+            f.len[j] = (uint32_t)ea.job.len_out;
+            f.flags_out[j] = ea.job.flags_out;
+            if (two) {
+                f.len[j + 1u] = (uint32_t)eb.job.len_out;
+                f.flags_out[j + 1u] = eb.job.flags_out;
+            }
+            const unsigned long long sk = (unsigned long long)(ea.job.by_source + (two ? eb.job.by_source : 0));
+            if (sk) atomicAdd(f.skipped, sk);
+        }
+        const uint32_t wa = (uint32_t)ea.job.copy_bytes / 16u, wb = two ? (uint32_t)eb.job.copy_bytes / 16u : 0u;
+        if ((wa | wb) == 0u) continue; // no work: no pointer is formed
+        // an entry without bytes borrows the other's pointers; its loads and stores are all predicated off
+        const uint32_t ja = wa ? j : j + 1u, jb = wb ? j + 1u : j;
+        const uint4 *fa = reinterpret_cast<const uint4 *>(f.src_seg + (wa ? ea.src_at : eb.src_at));
+        const uint4 *fb = reinterpret_cast<const uint4 *>(f.src_seg + (wb ? eb.src_at : ea.src_at));
+        uint4 *ta = reinterpret_cast<uint4 *>(f.seg + f.off[ja]);
+        uint4 *tb = reinterpret_cast<uint4 *>(f.seg + f.off[jb]);
+        for (uint32_t o = lane; o < max(wa, wb); o += 128u) {
+            const bool a0 = o < wa, a1 = o + 64u < wa, b0 = o < wb, b1 = o + 64u < wb;
+            uint4 x0, x1, y0, y1;
+            if (a0) x0 = fa[o];
+            if (a1) x1 = fa[o + 64u];
+            if (b0) y0 = fb[o];
+            if (b1) y1 = fb[o + 64u];
+            if (a0) ta[o] = x0;
+            if (a1) ta[o + 64u] = x1;
+            if (b0) tb[o] = y0;
+            if (b1) tb[o + 64u] = y1;
+        }
+    }
+}
+
+hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s) {
+    if (f.n == 0) return hipSuccess;
+    const uint32_t wgs = std::min<uint32_t>((f.n + 7u) / 8u, 4096u); // two entries per wave
+    hipLaunchKernelGGL(k_fanout, dim3(wgs), dim3(kGatherBlock), 0, s, f);
     return hipGetLastError();
 }
 

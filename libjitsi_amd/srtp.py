@@ -381,6 +381,80 @@ class SRTPEngine:
             cap.data_ptr(), None if flags is None else flags.data_ptr(), status.data_ptr(), n, sp)
         N.check(rc, self.h, "srtp_transform_device")
 
+    # -- fan-out: one packet to many peers -----------------------------------
+    def fanout_device(self, tid, src_seg, src_off, src_len, src_cap, src_idx, seg, off, length, cap, status,
+                      src_status=None, flags=None, m: Optional[int] = None, n: Optional[int] = None,
+                      stream=None) -> None:
+        """srtp_fanout_device over torch tensors on this engine's GPU: the m
+        sources (``src_seg`` uint8, ``src_off`` / ``src_len`` / ``src_cap``
+        4-byte ints, ``src_status`` int32 or None) are expanded on the device
+        into the n destination entries (entry j: a copy of source
+        ``src_idx[j]`` in region ``off[j]`` / ``cap[j]`` of ``seg``) and
+        protected as one bundle under ``tid`` (an int, or an int32 tensor with
+        one transformer id per entry).  ``length`` and ``status`` are outputs.
+        ``src_len`` / ``src_status`` may be the ``length`` / ``status`` tensors
+        of a ``transform_device(reverse=True)`` enqueued before on the same
+        stream.  Async on ``stream`` like :meth:`transform_device`."""
+        if m is None:
+            m = src_off.numel()
+        if n is None:
+            n = off.numel()
+        if np.isscalar(tid):
+            tids_p, tid0 = None, int(tid)
+        else:
+            tids_p, tid0 = tid.data_ptr(), -1
+        sp = getattr(stream, "cuda_stream", stream)
+        rc = N.lib().srtp_fanout_device(
+            self.h, src_seg.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), src_cap.data_ptr(),
+            None if src_status is None else src_status.data_ptr(), m, src_idx.data_ptr(), tids_p, tid0,
+            seg.data_ptr(), off.data_ptr(), length.data_ptr(), cap.data_ptr(),
+            None if flags is None else flags.data_ptr(), status.data_ptr(), n, sp)
+        N.check(rc, self.h, "srtp_fanout_device")
+
+    def fanout_host(self, tid, src_seg: np.ndarray, src_off, src_len, src_cap, src_idx, seg: np.ndarray, off,
+                    cap, src_status=None, flags=None):
+        """srtp_fanout_host over numpy: only the source segment and the small
+        arrays cross to the device.  ``seg`` is output only -- afterwards the
+        bytes ``[off[j], off[j] + length[j])`` of the entries with status OK
+        are defined, every other byte of it is unspecified.  Returns
+        ``(length, status)``."""
+        assert src_seg.dtype == np.uint8 and src_seg.flags.c_contiguous
+        assert seg.dtype == np.uint8 and seg.flags.c_contiguous and seg.flags.writeable
+        src_off = np.ascontiguousarray(src_off, np.uint32)
+        src_len = np.ascontiguousarray(src_len, np.uint32)
+        src_cap = np.ascontiguousarray(src_cap, np.uint32)
+        src_idx = np.ascontiguousarray(src_idx, np.int32)
+        off = np.ascontiguousarray(off, np.uint32)
+        cap = np.ascontiguousarray(cap, np.uint32)
+        m, n = len(src_off), len(off)
+        assert len(src_len) == m and len(src_cap) == m and len(src_idx) == n and len(cap) == n
+        st_in = None if src_status is None else np.ascontiguousarray(src_status, np.int32)
+        fl = None if flags is None else np.ascontiguousarray(flags, np.uint32)
+        assert (st_in is None or len(st_in) == m) and (fl is None or len(fl) == n)
+        if np.isscalar(tid):
+            tids_p, tid0 = None, int(tid)
+        else:
+            tids = np.ascontiguousarray(tid, np.int32)
+            assert len(tids) == n
+            tids_p, tid0 = tids.ctypes.data, -1
+        length = np.zeros(n, np.uint32)
+        status = np.zeros(n, np.int32)
+        rc = N.lib().srtp_fanout_host(
+            self.h, src_seg.ctypes.data, src_seg.nbytes, src_off.ctypes.data, src_len.ctypes.data,
+            src_cap.ctypes.data, None if st_in is None else st_in.ctypes.data, m, src_idx.ctypes.data, tids_p,
+            tid0, seg.ctypes.data, seg.nbytes, off.ctypes.data, length.ctypes.data, cap.ctypes.data,
+            None if fl is None else fl.ctypes.data, status.ctypes.data, n)
+        N.check(rc, self.h, "srtp_fanout_host")
+        return length, status
+
+    def fanout_stats(self) -> dict:
+        """srtp_engine_fanout_stats: fan-out calls, their sources and
+        destination entries, the entries skipped for their index or their
+        source's status, and the source bytes fanout_host copied to the device."""
+        st = N.FanoutStats()
+        N.check(N.lib().srtp_engine_fanout_stats(self.h, C.byref(st)), self.h, "fanout_stats")
+        return st.as_dict()
+
 
 def host_register(arr: np.ndarray) -> None:
     """Pins ``arr``'s memory for DMA by every GPU (srtp_host_register): a
@@ -1154,6 +1228,61 @@ class SRTCPTransformer(_SRTPBase):
 
     def updateFactory(self, factory: SRTPContextFactory, forward: bool):
         self._set_factory(factory, forward)
+
+
+def fan_out(pkts: Sequence[Optional[RawPacket]], transformers: Sequence[_SRTPBase], exclusion=None):
+    """One packet to many peers: what OutputDataStreamImpl.doWrite
+    (rtp/translator/OutputDataStreamImpl.java:171-243) does with each packet --
+    it loops over the streams and hands the same ``buf, off, len`` to each, and
+    each stream's connector copies it and runs its own transformer's
+    ``transform`` -- for a list of packets and the streams' transformers (all of
+    one SRTPEngine), with the copies made on the GPU (srtp_fanout_host): each
+    packet crosses to the device once.  Entries are processed in doWrite's
+    order, packet by packet and, within a packet, stream by stream, as one
+    bundle: toward each transformer the result is that of its
+    ``transform(copies of pkts)``, except that a copy on which the reference
+    would throw is answered with None instead of an exception (and, on an
+    engine with abort_on_error, so are the later copies toward that
+    transformer, SinglePacketTransformer.java:121-216).
+    ``exclusion``: a transformer, or one (or None) per packet -- the stream the
+    packet came from, which doWrite passes over (:193-194).  ``None`` packets
+    are written to nobody.  The packets themselves are left as they are.
+    Returns one list per transformer: element i is the protected copy of
+    packet i as a new RawPacket, or None (not written, dropped, or thrown)."""
+    pkts, transformers = list(pkts), list(transformers)
+    out = [[None] * len(pkts) for _ in transformers]
+    if not pkts or not transformers:
+        return out
+    eng = transformers[0].engine
+    if not isinstance(eng, SRTPEngine) or any(t.engine is not eng for t in transformers):
+        raise ValueError("fan_out: the transformers of one SRTPEngine")
+    excl = list(exclusion) if isinstance(exclusion, (list, tuple)) else [exclusion] * len(pkts)
+    room = eng.trailer_room
+    src_seg, src_off, src_len, src_cap, src_flags = pack(pkts, reverse=True)
+    src_status = np.where(src_flags & N.PKT_FLAG_SKIP, N.STATUS_SKIPPED, N.STATUS_OK).astype(np.int32)
+    T = len(transformers)
+    src_idx = np.repeat(np.arange(len(pkts), dtype=np.int32), T)
+    tids = np.tile(np.array([t.tid for t in transformers], np.int32), len(pkts))
+    # a copy's buffer holds the packet and the trailer (RawPacket.append / grow)
+    cap = np.repeat(np.maximum(src_cap, src_len + room), T).astype(np.uint32)
+    flags = np.repeat(src_flags & (N.PKT_FLAG_DISCARD | N.PKT_FLAG_SILENCE), T).astype(np.uint32)
+    for i, x in enumerate(excl):
+        for k, t in enumerate(transformers):
+            if x is t or (t.packetPredicate is not None and pkts[i] is not None
+                          and not t.packetPredicate(pkts[i])):
+                flags[i * T + k] |= N.PKT_FLAG_SKIP
+    step = (cap.astype(np.int64) + 15) & ~15
+    off = np.concatenate(([0], np.cumsum(step)[:-1])).astype(np.int64)
+    if int(off[-1] + step[-1]) >= 1 << 32:
+        raise ValueError("fan_out: more than 4 GiB of copies")
+    seg = np.zeros(int(off[-1] + step[-1]), np.uint8)
+    ln, st = eng.fanout_host(tids, src_seg, src_off, src_len, src_cap, src_idx, seg, off.astype(np.uint32), cap,
+                             src_status, flags)
+    for j in np.nonzero(st == N.STATUS_OK)[0]:
+        i, k = divmod(int(j), T)
+        o = int(off[j])
+        out[k][i] = RawPacket(seg[o:o + int(ln[j])].tobytes(), 0, int(ln[j]), pkts[i].flags)
+    return out
 
 
 def transform_bundle(transformers: Sequence[Optional[_SRTPBase]], pkts, reverse: bool):

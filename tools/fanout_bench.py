@@ -1,0 +1,239 @@
+#!/usr/bin/env python3
+"""Fan-out on the device against the routes the engine offered before it.
+
+  --host    2^16 destinations of 1200-byte sources, N in {1, 2, 4, 8, 16} peers,
+            AES_CM_128_HMAC_SHA1_80 and AEAD_AES_128_GCM: SRTPEngine.fanout_host
+            against host expansion into a pinned segment (timed: the application
+            pays it) plus transform_host.  Both routes interleaved on one engine,
+            5 warm-up and 20 timed calls each, wall-clock medians with p10 / p90
+            and the host-to-device bytes of a call; per N, whether the medians
+            differ by more than the wider of the two spreads.
+  --device  n = 2^18, N = 8: fanout_device against transform_device on a
+            pre-expanded bundle, HIP events; and a plain device copy of the bytes
+            k_fanout writes, in the same process.
+  --once    three fanout_device calls of the --device shape and nothing else
+            (for a kernel trace of k_fanout in a run of its own).
+
+Every call gets sources with new sequence numbers (not timed, for either
+route), so that no destination is a replay.  One JSON document on stdout, or
+in --out."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from libjitsi_amd import (HostBuffer, SRTPContextFactory, SRTPEngine, SRTPTransformer,  # noqa: E402
+                          profile_policies)
+
+LEN, SRC_STRIDE, ROOM = 1200, 1200, 20
+DST_CAP = LEN + ROOM
+DST_STRIDE = (DST_CAP + 15) & ~15
+WARM, TIMED = 5, 20
+
+
+def peers(eng, profile, count):
+    rng = np.random.default_rng(11)
+    gcm = profile.startswith("AEAD")
+    out = []
+    for _ in range(count):
+        mk = rng.integers(0, 256, 16, dtype=np.uint8).tobytes()
+        ms = rng.integers(0, 256, 12 if gcm else 14, dtype=np.uint8).tobytes()
+        out.append(SRTPTransformer(SRTPContextFactory(True, mk, ms, *profile_policies(profile), engine=eng)))
+    return out
+
+
+class Sources:
+    """m RTP packets of LEN bytes over up to 4096 SSRCs; advance() gives every one a new sequence number."""
+
+    def __init__(self, m, seg):
+        self.m, self.ssrcs = m, min(m, 4096)
+        self.seg = seg
+        self.rows = seg[:m * SRC_STRIDE].reshape(m, SRC_STRIDE)
+        self.rows[:] = np.random.default_rng(5).integers(0, 256, (m, SRC_STRIDE), dtype=np.uint8)
+        self.rows[:, 0], self.rows[:, 1] = 0x80, 96
+        ssrc = (0x10000 + np.arange(m) % self.ssrcs).astype(">u4")
+        self.rows[:, 8:12] = ssrc.view(np.uint8).reshape(m, 4)
+        self.per_call = (m + self.ssrcs - 1) // self.ssrcs
+        self.base = 1
+        self.off = (np.arange(m) * SRC_STRIDE).astype(np.uint32)
+        self.len = np.full(m, LEN, np.uint32)
+        self.cap = np.full(m, SRC_STRIDE, np.uint32)
+        self.advance()
+
+    def advance(self):
+        seq = ((self.base + np.arange(self.m) // self.ssrcs) & 0xFFFF).astype(">u2")
+        self.rows[:, 2:4] = seq.view(np.uint8).reshape(self.m, 2)
+        self.base += self.per_call
+
+
+def pct(xs):
+    xs = np.sort(np.array(xs))
+    return {"median_ms": float(np.median(xs)), "p10_ms": float(np.percentile(xs, 10)),
+            "p90_ms": float(np.percentile(xs, 90))}
+
+
+def verdict(a, b):
+    """a: fan-out, b: the other route."""
+    spread = max(a["p90_ms"] - a["p10_ms"], b["p90_ms"] - b["p10_ms"])
+    d = b["median_ms"] - a["median_ms"]
+    return "fan-out faster" if d > spread else "fan-out slower" if -d > spread else "no difference beyond the spread"
+
+
+def host_case(eng, profile, n, fan):
+    m = n // fan
+    ts = peers(eng, profile, fan)
+    hs, hd = HostBuffer(m * SRC_STRIDE), HostBuffer(n * DST_STRIDE)
+    src = Sources(m, hs.array)
+    src_idx = np.repeat(np.arange(m, dtype=np.int32), fan)  # source-major, doWrite's order
+    tids = np.tile(np.array([t.tid for t in ts], np.int32), m)
+    off = (np.arange(n, dtype=np.int64) * DST_STRIDE).astype(np.uint32)
+    cap = np.full(n, DST_CAP, np.uint32)
+    dst_rows = hd.array.reshape(n, DST_STRIDE)
+    t_fan, t_old, t_expand = [], [], []
+    for it in range(WARM + TIMED):
+        src.advance()
+        t0 = time.perf_counter()
+        ln, st = eng.fanout_host(tids, src.seg, src.off, src.len, src.cap, src_idx, hd.array, off, cap)
+        t1 = time.perf_counter()
+        assert not st.any() and (ln == LEN + (16 if profile.startswith("AEAD") else 10)).all()
+        src.advance()
+        t2 = time.perf_counter()
+        dst_rows[:, :LEN] = src.rows[src_idx]  # the N host-made copies
+        ln = np.full(n, LEN, np.uint32)
+        t3 = time.perf_counter()
+        st = eng.transform_host(False, tids, hd.array, off, ln, cap)
+        t4 = time.perf_counter()
+        assert not st.any()
+        if it >= WARM:
+            t_fan.append((t1 - t0) * 1e3)
+            t_old.append((t4 - t2) * 1e3)
+            t_expand.append((t3 - t2) * 1e3)
+    for t in ts:
+        t.close()
+    hs.close()
+    hd.close()
+    a, b = pct(t_fan), pct(t_old)
+    small = 4 * n  # a uint32 / int32 array of n entries
+    return {"profile": profile, "N": fan, "n": n, "m": m, "fanout_host": a, "expand_plus_transform_host": b,
+            "host_expansion_alone": pct(t_expand),
+            "h2d_bytes_fanout": m * SRC_STRIDE + 3 * 4 * m + 4 * small,  # sources, their 3 arrays; idx, off, cap, tids
+            "h2d_bytes_expand": n * DST_STRIDE + 4 * small,              # the copies; off, len, cap, tids
+            "verdict": verdict(a, b)}
+
+
+def device_case(eng, n, fan, once):
+    import torch
+    m = n // fan
+    ts = peers(eng, "AES_CM_128_HMAC_SHA1_80", fan)
+    src = Sources(m, np.zeros(m * SRC_STRIDE, np.uint8))
+    d = lambda a: torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).cuda()
+    src_idx = np.repeat(np.arange(m, dtype=np.int32), fan)
+    tids = d(np.tile(np.array([t.tid for t in ts], np.int32), m))
+    off = d((np.arange(n, dtype=np.int64) * DST_STRIDE).astype(np.uint32))
+    cap, s_off, s_len, s_cap, idx = d(np.full(n, DST_CAP, np.uint32)), d(src.off), d(src.len), d(src.cap), d(src_idx)
+    seg = torch.zeros(n * DST_STRIDE, dtype=torch.uint8, device="cuda")
+    ln = torch.zeros(n, dtype=torch.int32, device="cuda")
+    st = torch.zeros(n, dtype=torch.int32, device="cuda")
+    idx64 = idx.long()
+    stream = torch.cuda.Stream()
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+
+    def fresh():
+        src.advance()
+        return d(src.seg)
+
+    def fan_call(s_seg):
+        eng.fanout_device(tids, s_seg, s_off, s_len, s_cap, idx, seg, off, ln, cap, st, stream=stream)
+
+    if once:
+        for _ in range(3):
+            s_seg = fresh()
+            torch.cuda.synchronize()
+            fan_call(s_seg)
+            eng.sync(stream.cuda_stream)
+        assert not st.any().item()
+        return {"once": 3, "n": n, "m": m}
+    t_fan, t_old, t_copy = [], [], []
+    plain_src = torch.zeros(n * LEN, dtype=torch.uint8, device="cuda")
+    plain_dst = torch.zeros(n * LEN, dtype=torch.uint8, device="cuda")
+    for it in range(WARM + TIMED):
+        s_seg = fresh()
+        torch.cuda.synchronize()
+        a, b = ev(), ev()
+        with torch.cuda.stream(stream):
+            a.record()
+            fan_call(s_seg)
+            b.record()
+        b.synchronize()
+        eng.sync(stream.cuda_stream)
+        assert not st.any().item()
+        # the pre-expanded bundle: the copies made beforehand, outside the timing
+        s_seg = fresh()
+        seg.view(n, DST_STRIDE)[:, :LEN] = s_seg.view(m, SRC_STRIDE)[idx64]
+        ln.fill_(LEN)
+        torch.cuda.synchronize()
+        c, e = ev(), ev()
+        with torch.cuda.stream(stream):
+            c.record()
+            eng.transform_device(False, tids, seg, off, ln, cap, st, stream=stream)
+            e.record()
+        e.synchronize()
+        eng.sync(stream.cuda_stream)
+        assert not st.any().item()
+        f, g = ev(), ev()
+        with torch.cuda.stream(stream):
+            f.record()
+            plain_dst.copy_(plain_src)
+            g.record()
+        g.synchronize()
+        if it >= WARM:
+            t_fan.append(a.elapsed_time(b))
+            t_old.append(c.elapsed_time(e))
+            t_copy.append(f.elapsed_time(g))
+    pa, pb, pc = pct(t_fan), pct(t_old), pct(t_copy)
+    moved = n * LEN + m * LEN  # bytes k_fanout writes + distinct bytes it reads
+    return {"n": n, "N": fan, "m": m, "fanout_device": pa, "transform_device_pre_expanded": pb,
+            "plain_device_copy_of_n_x_1200_bytes": pc,
+            "plain_copy_GBps_read_plus_written": 2 * n * LEN / (pc["median_ms"] * 1e6),
+            "k_fanout_bytes_moved": moved,
+            "k_fanout_ms_by_difference_of_medians": pa["median_ms"] - pb["median_ms"],
+            "packets_per_s_fanout": n / (pa["median_ms"] * 1e-3),
+            "packets_per_s_pre_expanded": n / (pb["median_ms"] * 1e-3)}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--host", action="store_true")
+    ap.add_argument("--device", action="store_true")
+    ap.add_argument("--once", action="store_true")
+    ap.add_argument("--log2n-host", type=int, default=16)
+    ap.add_argument("--log2n-device", type=int, default=18)
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    if args.device or args.once:
+        import torch  # asked before the engine library initialises HIP: torch caches its first answer
+        assert torch.cuda.is_available()
+    eng = SRTPEngine(device=0, max_contexts=1 << 19, max_factories=256, max_transformers=256,
+                     max_batch=1 << max(args.log2n_host, args.log2n_device))
+    eng.enable_aead()
+    res = {}
+    if args.host:
+        res["host"] = [host_case(eng, prof, 1 << args.log2n_host, fan)
+                       for prof in ("AES_CM_128_HMAC_SHA1_80", "AEAD_AES_128_GCM") for fan in (1, 2, 4, 8, 16)]
+    if args.device or args.once:
+        res["device"] = device_case(eng, 1 << args.log2n_device, 8, args.once)
+    res["fanout_stats"] = eng.fanout_stats()
+    eng.close()
+    text = json.dumps(res, indent=1)
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(text + "\n")
+    print(text)
+
+
+if __name__ == "__main__":
+    main()
