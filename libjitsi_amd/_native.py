@@ -96,7 +96,7 @@ STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 # Sources that decide what the crypto kernels execute: the key that ties
 # committed PMC counters (profiles/pmc_traffic.json) to the build they measured.
 KERNEL_SOURCES = ["srtp_kernels.hip", "aes_rounds_asm.inc", "srtp_kernels.h", "srtp_types.h", "engine.cpp",
-                  "gcm_job.h", "fanout_job.h"]
+                  "gcm_job.h", "fanout_job.h", "bundle_plan.h"]
 
 
 def kernel_source_sha16() -> str:

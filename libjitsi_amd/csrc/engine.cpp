@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <new>
@@ -128,16 +129,6 @@ struct srtp_engine {
 };
 
 namespace {
-constexpr uint32_t kSmallCtrMax = 8192u; // k_ctr_small takes bundles up to this size
-// The split path (k_ctr_wide + k_mac_wide) for bundles of kWideMin..kWideMax
-// packets: there the fused kernels' lane per packet leaves most CUs idle or
-// latency-bound; from 2^17 packets on the fused kernels are faster
-// (profiles/r06/kernel_experiments.md, bundle-size sweep)
-#ifndef SRTP_WIDE_MIN
-#define SRTP_WIDE_MIN 2048u
-#endif
-constexpr uint32_t kWideMin = SRTP_WIDE_MIN, kWideMax = 65536u;
-
 int fail(srtp_engine *e, int code, const std::string &msg) {
     if (e) e->last_error = msg;
     return code;
@@ -156,6 +147,20 @@ template <class T> hipError_t dalloc(T **p, size_t count) {
 
 void dfree(void *p) {
     if (p) (void)hipFree(p);
+}
+
+// A staging set (device arrays of *have elements each) grows to `want`: freed,
+// null and *have 0 until every new allocation stands.  The caller has quiesced
+// whatever may still use the old arrays.
+template <class Size, class... T> int grow_staging(srtp_engine *e, Size *have, Size want, T **...arrays) {
+    if (want <= *have) return SRTP_OK;
+    ((dfree(*arrays), *arrays = nullptr), ...);
+    *have = 0;
+    hipError_t err = hipSuccess;
+    ((err = err != hipSuccess ? err : dalloc(arrays, want)), ...);
+    HIPCHK(e, err);
+    *have = want;
+    return SRTP_OK;
 }
 
 // Profiles the engine implements: AES-CM with a 128- or 256-bit key, AES-F8
@@ -803,33 +808,80 @@ int srtp_transformer_close(srtp_engine *e, int32_t t) {
     return SRTP_OK;
 }
 
-// A bundle of up to kSmallMaxN packets of an engine whose key sets are all the
-// split path's or AES-GCM ones runs every phase in one launch (k_small; once the
-// engine holds a GCM key set its GCM instance, up to kSmallGcmMax packets),
-// unless a debug hook needs the multi-kernel chain (the GCM route hooks:
-// k_gcm_wave / k_gcm).
-static bool small_path(const srtp_engine *e, uint32_t n) {
-    const uint32_t lim = e->n_gcm && !(e->dbg & SRTP_DEBUG_FORCE_SMALL) ? kSmallGcmMax : kSmallMaxN;
-    return e->n_not_small == 0 && n <= lim &&
-           !(e->dbg & (SRTP_DEBUG_FORCE_CHAIN_STALL | SRTP_DEBUG_NO_WIDE | SRTP_DEBUG_FORCE_WIDE | SRTP_DEBUG_NO_SMALL |
-                       SRTP_DEBUG_NO_GCM_WAVE | SRTP_DEBUG_FORCE_GCM_WAVE));
+// What a bundle's route depends on (bundle_plan.h decides it, and nothing here).
+static EngineShape engine_shape(const srtp_engine *e) {
+    static_assert(SRTP_DEBUG_FORCE_CHAIN_STALL == kPlanDbgForceChainStall && SRTP_DEBUG_FORCE_WIDE == kPlanDbgForceWide &&
+                      SRTP_DEBUG_NO_WIDE == kPlanDbgNoWide && SRTP_DEBUG_NO_SMALL == kPlanDbgNoSmall &&
+                      SRTP_DEBUG_NO_GCM_WAVE == kPlanDbgNoGcmWave && SRTP_DEBUG_FORCE_GCM_WAVE == kPlanDbgForceGcmWave &&
+                      SRTP_DEBUG_FORCE_SMALL == kPlanDbgForceSmall && SRTP_DEBUG_NO_GCM_SPEC == kPlanDbgNoGcmSpec &&
+                      SRTP_DEBUG_FORCE_GCM_SPEC == kPlanDbgForceGcmSpec,
+                  "bundle_plan.h restates the debug flags");
+    static_assert(SRTP_STAGE_PARSE == kStageParse && SRTP_STAGE_SORT == kStageSort && SRTP_STAGE_VERIFY == kStageVerify &&
+                      SRTP_STAGE_WALK == kStageWalk && SRTP_STAGE_PROTECT == kStageProtect &&
+                      SRTP_STAGE_DECRYPT == kStageDecrypt,
+                  "bundle_plan.h restates the stages");
+    EngineShape sh;
+    sh.has_gcm = e->n_gcm != 0;
+    sh.has_skein = e->n_skein != 0;
+    sh.has_ext = e->n_ext != 0;
+    sh.all_wide = e->n_not_wide == 0;
+    sh.all_small = e->n_not_small == 0;
+    sh.ctx_bits = e->ctx_bits;
+    sh.dbg = e->dbg;
+    sh.sort_tile = sort_tile_records();
+    return sh;
+}
+
+// What every bundle entry point checks before its first device call.
+static int check_buffers(srtp_engine *e, std::initializer_list<const void *> ptrs) {
+    for (const void *p : ptrs)
+        if (!p) return fail(e, SRTP_EINVAL, "null buffer");
+    return SRTP_OK;
+}
+static int check_size(srtp_engine *e, uint32_t n) {
+    return n > kRecIdxMask ? fail(e, SRTP_EINVAL, "bundle too large") : SRTP_OK;
+}
+static int check_tid(srtp_engine *e, bool has_tids, int32_t tid) {
+    if (!has_tids && (tid < 0 || (size_t)tid >= e->transformers.size()))
+        return fail(e, SRTP_EINVAL, "bad transformer id");
+    return SRTP_OK;
+}
+
+static hipError_t launch_step(const BundleArgs &a, const SortScratch &ss, const BundlePlan &plan, const PlanStep &st,
+                              hipStream_t s) {
+    switch (st.launch) {
+    case kLaunchSmall: return launch_small(a, s);
+    case kLaunchParse: return launch_parse(a, s);
+    case kLaunchSortTile: return launch_sort_tile(a, s);
+    case kLaunchSort: return launch_sort(a, ss, s);
+    case kLaunchUnprotect: return launch_unprotect(a, s);
+    case kLaunchCtrSmall: return launch_ctr_small(a, s);
+    case kLaunchSkein: return launch_skein(a, s);
+    case kLaunchGcm: return launch_gcm(a, (GcmPass)st.pass, plan.gcm_wave, s);
+    case kLaunchWalk: return launch_walk(a, (WalkPass)st.pass, s);
+    case kLaunchUnprotectFix: return launch_unprotect_fix(a, s);
+    case kLaunchExt: return launch_ext(a, s);
+    case kLaunchProtect: return launch_protect(a, s);
+    case kLaunchCtrWide: return launch_ctr_wide(a, s);
+    case kLaunchMacWide: return launch_mac_wide(a, s);
+    }
+    return hipErrorInvalidValue;
 }
 
 // abort: SinglePacketTransformer's abort-on-throw for this bundle (-1: the
 // engine's abort_on_error; 0: every packet is its own 1-element array)
 // pk_host: k_small's direct mode (BundleArgs::pk_host); only for a bundle
-// small_path takes
+// whose path is kPathSmall
 static int transform_locked(srtp_engine *e, int32_t reverse, const int32_t *tids, int32_t tid,
                             uint8_t *seg, const uint32_t *off, uint32_t *len, const uint32_t *cap,
                             const uint32_t *flags, int32_t *status, uint32_t n, hipStream_t s,
                             int32_t abort = -1, bool dev_event = false, const uint8_t *pk_host = nullptr,
                             uint8_t *pk_dev = nullptr, uint32_t pk_bytes = 0) {
     if (n == 0) return SRTP_OK;
-    if (!seg || !off || !len || !cap || !status) return fail(e, SRTP_EINVAL, "null buffer");
-    if (n > kRecIdxMask) return fail(e, SRTP_EINVAL, "bundle too large");
-    if (!tids && (tid < 0 || (size_t)tid >= e->transformers.size()))
-        return fail(e, SRTP_EINVAL, "bad transformer id");
-    int rc = ensure_scratch(e, n);
+    int rc = check_buffers(e, {seg, off, len, cap, status});
+    if (rc == SRTP_OK) rc = check_size(e, n);
+    if (rc == SRTP_OK) rc = check_tid(e, tids != nullptr, tid);
+    if (rc == SRTP_OK) rc = ensure_scratch(e, n);
     if (rc != SRTP_OK) return rc;
     // bundles of one engine share its scratch and run in submission order: a
     // bundle on another stream than the previous one waits for it on the device
@@ -842,16 +894,7 @@ static int transform_locked(srtp_engine *e, int32_t reverse, const int32_t *tids
     a.has_skein = e->n_skein ? 1 : 0;
     a.gcmkeys = e->d_gcmkeys;
     a.gcmpow = e->d_gcmpow;
-    a.gcm_route = (e->dbg & SRTP_DEBUG_NO_GCM_WAVE) ? kGcmRouteLane : (e->dbg & SRTP_DEBUG_FORCE_GCM_WAVE) ? kGcmRouteWave : 0;
     a.has_gcm = e->n_gcm ? 1 : 0;
-    // the one-pass open: where the sweep made it the default on the route this
-    // bundle takes (srtp_kernels.h), or as the hooks say
-    const bool gcm_wave = a.gcm_route ? a.gcm_route == kGcmRouteWave : n <= kGcmWaveMax; // launch_gcm's rule
-    const bool gcm_spec = !e->n_gcm || (e->dbg & SRTP_DEBUG_NO_GCM_SPEC) ? false
-                          : (e->dbg & SRTP_DEBUG_FORCE_GCM_SPEC)         ? true
-                          : gcm_wave ? n >= kGcmOpenWaveMin && n <= kGcmOpenWaveMax
-                                     : n >= kGcmOpenLaneMin;
-    if (gcm_spec) a.gcm_route |= kGcmRouteSpec;
     a.factories = e->d_factories;
     a.transformers = e->d_transformers;
     a.ctx_keys = e->d_ctx_keys;
@@ -881,45 +924,36 @@ static int transform_locked(srtp_engine *e, int32_t reverse, const int32_t *tids
     a.spos = e->spos;
     a.lord = e->lord;
     a.cls_tile = e->cls_tile;
-    const SortScratch ss = sort_scratch(e->sort_temp, e->scratch_n);
-    // keys: slot or ctx_cap (= not walked), ctx_bits + 1 bits: 8-bit digits up
-    // to 16 bits, two 9-11-bit digits up to 22 (the wide sort), else 8-bit again
-    // 17-19 bits: an 8-bit pass and one wide pass (hybrid); 20-22: two wide
-    // passes (profiles/r04/kernel_experiments.md 8)
-    const int key_bits = e->ctx_bits + 1;
-    const bool big = key_bits > 16 && key_bits <= 2 * kSortWideMaxBits;
-    const bool hybrid = big && key_bits <= 8 + kSortWideMaxBits;
-    const bool wide = big && !hybrid;
-    a.sort_key_bits = key_bits;
-    a.sort_hi_bits = hybrid ? key_bits - 8 : 0;
-    a.sort_passes = big ? 2 : (key_bits + 7) / 8;
-    a.sort_bits = wide ? (key_bits + 1) / 2 : 8;
-    a.sort_counts = wide ? ss.wcounts[0] : ss.counts[0];
-    // the walk re-zeroes the 8-bit sort's last counts, and the hybrid's first
-    // (k_parse's); the wide sort's k_sort_prefix zeroes its own (the walk then
-    // clears a prefix table that is rewritten before its next use)
-    a.sort_zero = wide ? ss.wprefix : hybrid ? ss.counts[0] : ss.counts[a.sort_passes - 1];
-    a.sort_zero_words = ((n + sort_tile_records() - 1u) / sort_tile_records()) * 256u; // tiles of this bundle x 256 digits
-    // a small bundle's AES-CM keystream by k_ctr_small (a lane per counter-block
-    // pair; the fused kernels only MAC): up to 8192 packets (128 waves: under
-    // one wave per SIMD; profiles/r04/kernel_experiments.md 9)
-    // Mid-size bundles of engines whose key sets are all AES-CM / NULL cipher +
-    // HMAC-SHA1 take the split path (k_ctr_wide + k_mac_wide, srtp_kernels.hip),
-    // the rest the fused kernels (with k_ctr_small up to kSmallCtrMax packets).
-    const bool wide_ok = e->n_not_wide == 0 && !(e->dbg & SRTP_DEBUG_NO_WIDE);
-    const bool split = wide_ok && ((n >= kWideMin && n <= kWideMax) || (e->dbg & SRTP_DEBUG_FORCE_WIDE));
-    const bool small = small_path(e, n);
-    if (pk_host && !small) return fail(e, SRTP_EINVAL, "direct mode without k_small");
-    a.pk_host = small ? pk_host : nullptr;
     a.pk_dev = pk_dev;
     a.pk_bytes = pk_bytes;
-    a.small_ctr = split || small ? 2 : n <= kSmallCtrMax ? 1 : 0;
     const int c = e->ctl_cur;
     const size_t nt_max = e->opts.max_transformers;
     a.ctl = e->ctl + c;
     a.e_min = e->e_min + c * nt_max;
     a.ctl_next = e->ctl + (c ^ 1);
     a.e_min_next = e->e_min + (c ^ 1) * nt_max;
+
+    // the route: which kernels run, in which order (bundle_plan.h)
+    const BundlePlan plan = plan_bundle(engine_shape(e), n, a.reverse, a.abort_on_error);
+    if (plan.n_steps > kPlanMaxSteps) return fail(e, SRTP_EINVAL, "bundle plan too long");
+    const bool small = plan.path == kPathSmall;
+    if (pk_host && !small) return fail(e, SRTP_EINVAL, "direct mode without k_small");
+    a.pk_host = pk_host;
+    a.gcm_route = plan.gcm_route;
+    a.small_ctr = plan.small_ctr;
+    a.sort_key_bits = plan.sort_key_bits;
+    a.sort_hi_bits = plan.sort_hi_bits;
+    a.sort_passes = plan.sort_passes;
+    a.sort_bits = plan.sort_bits;
+    const SortScratch ss = sort_scratch(e->sort_temp, e->scratch_n);
+    const bool wide = plan.sort_kind == kSortWide, hybrid = plan.sort_kind == kSortHybrid;
+    a.sort_counts = wide ? ss.wcounts[0] : ss.counts[0];
+    // the walk re-zeroes the 8-bit sort's last counts, and the hybrid's first
+    // (k_parse's); the wide sort's k_sort_prefix zeroes its own (the walk then
+    // clears a prefix table that is rewritten before its next use)
+    a.sort_zero = wide ? ss.wprefix : hybrid ? ss.counts[0] : ss.counts[a.sort_passes - 1];
+    a.sort_zero_words = ((n + sort_tile_records() - 1u) / sort_tile_records()) * 256u; // tiles of this bundle x 256 digits
+
     const bool need_ctl = !e->ctl_clean[c];
     const bool need_emin = a.abort_on_error && e->emin_filled[c] < a.n_transformers;
     e->ctl_clean[c] = false; // this bundle's atomics dirty it
@@ -928,72 +962,20 @@ static int transform_locked(srtp_engine *e, int32_t reverse, const int32_t *tids
     if (a.abort_on_error) e->emin_filled[c] = 0u;
     if (need_ctl) HIPCHK(e, hipMemsetAsync(a.ctl, 0, sizeof(BundleCtl), s));
     if (need_emin) HIPCHK(e, hipMemsetAsync(a.e_min, 0x7f, sizeof(int32_t) * a.n_transformers, s));
-    if (small) {
-        StageTimer t(e, s, a.reverse ? SRTP_STAGE_VERIFY : SRTP_STAGE_PROTECT);
-        HIPCHK(e, launch_small(a, s)); // also resets control block c ^ 1 (and e_min c ^ 1)
-        e->ctl_clean[c ^ 1] = true;
-        if (a.abort_on_error) e->emin_filled[c ^ 1] = a.n_transformers;
-        e->ctl_cur = c ^ 1;
-        if (e->n_gcm) e->n_small_aead++;
-        else e->n_small++;
-    } else {
-    // a one-tile bundle is sorted by one workgroup in one launch
-    const bool one_tile = n <= sort_tile_records();
-    {
-        StageTimer t(e, s, SRTP_STAGE_PARSE);
-        // also resets control block c ^ 1
-        HIPCHK(e, launch_parse(a, s));
+    // one timer per run of steps of one stage
+    for (int i = 0; i < plan.n_steps;) {
+        const int stage = plan.steps[i].stage;
+        StageTimer t(e, s, stage);
+        for (; i < plan.n_steps && plan.steps[i].stage == stage; i++) {
+            HIPCHK(e, launch_step(a, ss, plan, plan.steps[i], s));
+            if (i == 0) { // k_small or k_parse: it also resets control block c ^ 1 (and e_min c ^ 1)
+                e->ctl_clean[c ^ 1] = true;
+                if (a.abort_on_error) e->emin_filled[c ^ 1] = a.n_transformers;
+                e->ctl_cur = c ^ 1;
+            }
+        }
     }
-    e->ctl_clean[c ^ 1] = true;
-    if (a.abort_on_error) e->emin_filled[c ^ 1] = a.n_transformers;
-    e->ctl_cur = c ^ 1;
-    {
-        StageTimer t(e, s, SRTP_STAGE_SORT);
-        HIPCHK(e, one_tile ? launch_sort_tile(a, s) : launch_sort(a, ss, s));
-    }
-    if (a.reverse && a.small_ctr == 2) {
-        StageTimer t(e, s, SRTP_STAGE_VERIFY);
-        HIPCHK(e, launch_mac_wide(a, s)); // tag check under the ROC guess, no decryption yet
-    } else if (a.reverse) {
-        StageTimer t(e, s, SRTP_STAGE_VERIFY);
-        HIPCHK(e, launch_unprotect(a, s));
-        if (a.small_ctr) HIPCHK(e, launch_ctr_small(a, s)); // the speculative decryption
-        if (e->n_skein) HIPCHK(e, launch_skein(a, s));
-        // tag check under the ROC guess (3: and the decipher, in the same trip)
-        if (e->n_gcm) HIPCHK(e, launch_gcm(a, gcm_spec ? 3 : 1, s));
-    }
-    {
-        StageTimer t(e, s, SRTP_STAGE_WALK);
-        HIPCHK(e, launch_walk(a, 0, s));
-        // second pass: abort-on-throw's limit pass when a packet may throw,
-        // else the wave-parallel walk of context chains longer than the
-        // first pass's window (returns at once when there are none) -- which a
-        // bundle of fewer than kLongMin packets cannot hold: a small bundle
-        // without abort-on-throw saves the launch
-        if (a.abort_on_error || n >= kLongMin || a.dbg) HIPCHK(e, launch_walk(a, 1, s));
-    }
-    if (a.reverse && a.small_ctr == 2) {
-        StageTimer t(e, s, SRTP_STAGE_DECRYPT);
-        HIPCHK(e, launch_ctr_wide(a, s)); // final statuses, decryption under the walk's ROC
-    } else if (a.small_ctr == 2) {
-        StageTimer t(e, s, SRTP_STAGE_PROTECT);
-        HIPCHK(e, launch_ctr_wide(a, s)); // the keystream, then the MAC and trailer
-        HIPCHK(e, launch_mac_wide(a, s));
-    } else if (a.reverse) {
-        StageTimer t(e, s, SRTP_STAGE_DECRYPT);
-        HIPCHK(e, launch_unprotect_fix(a, s));
-        if (e->n_ext) HIPCHK(e, launch_ext(a, s));
-        // the accepted packets deciphered (4: only the verdicts the walk overturned repaired)
-        if (e->n_gcm) HIPCHK(e, launch_gcm(a, gcm_spec ? 4 : 2, s));
-    } else {
-        StageTimer t(e, s, SRTP_STAGE_PROTECT);
-        if (a.small_ctr) HIPCHK(e, launch_ctr_small(a, s)); // the keystream, then k_protect MACs
-        HIPCHK(e, launch_protect(a, s));
-        if (e->n_ext) HIPCHK(e, launch_ext(a, s));
-        if (e->n_skein) HIPCHK(e, launch_skein(a, s));
-        if (e->n_gcm) HIPCHK(e, launch_gcm(a, 0, s)); // sealed: tag, SRTCP's E|index word
-    }
-    }
+    if (small) (e->n_gcm ? e->n_small_aead : e->n_small)++;
     HIPCHK(e, hipEventRecord(dev_event ? e->ev_dev : e->ev_last, s));
     e->last_dev = dev_event;
     e->last_stream = s;
@@ -1039,28 +1021,9 @@ static int ensure_host_staging(srtp_engine *e, size_t seg_bytes, uint32_t n) {
         int qrc = quiesce(e);
         if (qrc != SRTP_OK) return qrc;
     }
-    if (need > e->h_seg_bytes) {
-        dfree(e->h_seg);
-        e->h_seg = nullptr;
-        e->h_seg_bytes = 0;
-        HIPCHK(e, hipMalloc(&e->h_seg, need));
-        e->h_seg_bytes = need;
-    }
-    if (n > e->h_n) {
-        void *ptrs[] = {e->h_off, e->h_len, e->h_cap, e->h_flags, e->h_status, e->h_tids};
-        for (void *p : ptrs) dfree(p);
-        e->h_off = e->h_len = e->h_cap = e->h_flags = nullptr;
-        e->h_status = e->h_tids = nullptr;
-        e->h_n = 0;
-        HIPCHK(e, dalloc(&e->h_off, n));
-        HIPCHK(e, dalloc(&e->h_len, n));
-        HIPCHK(e, dalloc(&e->h_cap, n));
-        HIPCHK(e, dalloc(&e->h_flags, n));
-        HIPCHK(e, dalloc(&e->h_status, n));
-        HIPCHK(e, dalloc(&e->h_tids, n));
-        e->h_n = n;
-    }
-    return SRTP_OK;
+    int rc = grow_staging(e, &e->h_seg_bytes, need, &e->h_seg);
+    if (rc != SRTP_OK) return rc;
+    return grow_staging(e, &e->h_n, n, &e->h_off, &e->h_len, &e->h_cap, &e->h_flags, &e->h_status, &e->h_tids);
 }
 
 int srtp_transform_host(srtp_engine *e, int32_t reverse, const int32_t *tids, int32_t tid,
@@ -1069,8 +1032,8 @@ int srtp_transform_host(srtp_engine *e, int32_t reverse, const int32_t *tids, in
     if (!e) return SRTP_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     if (n == 0) return SRTP_OK;
-    if (!seg || !off || !len || !cap || !status) return fail(e, SRTP_EINVAL, "null buffer");
-    int vr = validate_regions(e, off, cap, n, seg_bytes);
+    int vr = check_buffers(e, {seg, off, len, cap, status});
+    if (vr == SRTP_OK) vr = validate_regions(e, off, cap, n, seg_bytes);
     if (vr != SRTP_OK) return vr;
     GUARD(e);
     hipStream_t s = e->stream;
@@ -1098,30 +1061,30 @@ void *srtp_engine_stream(srtp_engine *e) { return e ? (void *)e->stream : nullpt
 // k_fanout in front of the protect chain, both on `s`.  The flags words the
 // chain reads are the engine's (fan_flags), so the expansion waits, like a
 // bundle, for the previous bundle of another stream.
+static int check_fanout(srtp_engine *e, std::initializer_list<const void *> ptrs, uint32_t m, uint32_t n) {
+    int rc = check_buffers(e, ptrs);
+    if (rc != SRTP_OK) return rc;
+    if (m == 0) return fail(e, SRTP_EINVAL, "fan-out without a source");
+    rc = check_size(e, n);
+    return rc != SRTP_OK ? rc : check_size(e, m);
+}
+
 static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
                          const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status, uint32_t m,
                          const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
                          const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
                          int32_t *status, uint32_t n, hipStream_t s, bool dev_event) {
-    if (!src_seg || !src_off || !src_len || !src_cap || !src_idx || !seg || !off || !len || !cap || !status)
-        return fail(e, SRTP_EINVAL, "null buffer");
-    if (m == 0) return fail(e, SRTP_EINVAL, "fan-out without a source");
-    if (n > kRecIdxMask || m > kRecIdxMask) return fail(e, SRTP_EINVAL, "bundle too large");
-    if (!tids && (tid < 0 || (size_t)tid >= e->transformers.size()))
-        return fail(e, SRTP_EINVAL, "bad transformer id");
-    int rc = ensure_scratch(e, n);
+    int rc = check_fanout(e, {src_seg, src_off, src_len, src_cap, src_idx, seg, off, len, cap, status}, m, n);
+    if (rc == SRTP_OK) rc = check_tid(e, tids != nullptr, tid);
+    if (rc == SRTP_OK) rc = ensure_scratch(e, n);
     if (rc != SRTP_OK) return rc;
     if (n > e->fan_n) {
         if (e->have_last) { // the old flags words may still be read by an enqueued bundle
             rc = quiesce(e);
             if (rc != SRTP_OK) return rc;
         }
-        dfree(e->fan_flags);
-        e->fan_flags = nullptr;
-        e->fan_n = 0;
-        const uint32_t want = std::max<uint32_t>(n, 1024);
-        HIPCHK(e, dalloc(&e->fan_flags, want));
-        e->fan_n = want;
+        rc = grow_staging(e, &e->fan_n, std::max<uint32_t>(n, 1024), &e->fan_flags);
+        if (rc != SRTP_OK) return rc;
     }
     if (!e->d_fan_skipped) {
         HIPCHK(e, dalloc(&e->d_fan_skipped, 1));
@@ -1164,53 +1127,27 @@ int srtp_fanout_host(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_byte
     if (!e) return SRTP_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     if (n == 0) return SRTP_OK;
-    if (!src_seg || !src_off || !src_len || !src_cap || !src_idx || !seg || !off || !len || !cap || !status)
-        return fail(e, SRTP_EINVAL, "null buffer");
-    if (m == 0) return fail(e, SRTP_EINVAL, "fan-out without a source");
-    if (n > kRecIdxMask || m > kRecIdxMask) return fail(e, SRTP_EINVAL, "bundle too large");
-    int vr = validate_regions(e, src_off, src_cap, m, src_seg_bytes);
-    if (vr != SRTP_OK) return vr;
-    vr = validate_regions(e, off, cap, n, seg_bytes);
-    if (vr != SRTP_OK) return vr;
+    int rc = check_fanout(e, {src_seg, src_off, src_len, src_cap, src_idx, seg, off, len, cap, status}, m, n);
+    if (rc == SRTP_OK) rc = validate_regions(e, src_off, src_cap, m, src_seg_bytes);
+    if (rc == SRTP_OK) rc = validate_regions(e, off, cap, n, seg_bytes);
+    if (rc != SRTP_OK) return rc;
     for (uint32_t j = 0; j < n; j++)
         if (src_idx[j] < 0 || (uint32_t)src_idx[j] >= m) return fail(e, SRTP_EINVAL, "src_idx[j] names no source");
-    if (!tids && (tid < 0 || (size_t)tid >= e->transformers.size()))
-        return fail(e, SRTP_EINVAL, "bad transformer id");
+    rc = check_tid(e, tids != nullptr, tid);
+    if (rc != SRTP_OK) return rc;
     GUARD(e);
     hipStream_t s = e->stream;
-    int rc = ensure_host_staging(e, seg_bytes, n);
+    rc = ensure_host_staging(e, seg_bytes, n);
     if (rc != SRTP_OK) return rc;
     const size_t need = (src_seg_bytes + 15) & ~(size_t)15;
     if ((need > e->hs_seg_bytes || m > e->hs_m || n > e->hs_n) && e->have_last) {
         rc = quiesce(e); // the source staging may still be read by an enqueued fan-out
         if (rc != SRTP_OK) return rc;
     }
-    if (need > e->hs_seg_bytes) {
-        dfree(e->hs_seg);
-        e->hs_seg = nullptr;
-        e->hs_seg_bytes = 0;
-        HIPCHK(e, hipMalloc(&e->hs_seg, need));
-        e->hs_seg_bytes = need;
-    }
-    if (m > e->hs_m) {
-        void *ptrs[] = {e->hs_off, e->hs_len, e->hs_cap, e->hs_status};
-        for (void *p : ptrs) dfree(p);
-        e->hs_off = e->hs_len = e->hs_cap = nullptr;
-        e->hs_status = nullptr;
-        e->hs_m = 0;
-        HIPCHK(e, dalloc(&e->hs_off, m));
-        HIPCHK(e, dalloc(&e->hs_len, m));
-        HIPCHK(e, dalloc(&e->hs_cap, m));
-        HIPCHK(e, dalloc(&e->hs_status, m));
-        e->hs_m = m;
-    }
-    if (n > e->hs_n) {
-        dfree(e->hs_idx);
-        e->hs_idx = nullptr;
-        e->hs_n = 0;
-        HIPCHK(e, dalloc(&e->hs_idx, n));
-        e->hs_n = n;
-    }
+    rc = grow_staging(e, &e->hs_seg_bytes, need, &e->hs_seg);
+    if (rc == SRTP_OK) rc = grow_staging(e, &e->hs_m, m, &e->hs_off, &e->hs_len, &e->hs_cap, &e->hs_status);
+    if (rc == SRTP_OK) rc = grow_staging(e, &e->hs_n, n, &e->hs_idx);
+    if (rc != SRTP_OK) return rc;
     // only the source segment and the small arrays cross to the device
     HIPCHK(e, hipMemcpyAsync(e->hs_seg, src_seg, src_seg_bytes, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(e->hs_off, src_off, m * 4ull, hipMemcpyHostToDevice, s));
@@ -2078,8 +2015,8 @@ static int pipeline_submit(srtp_pipeline *pl, int32_t slot, int32_t reverse, int
     std::lock_guard<std::mutex> g(e->mu);
     int rc = validate_regions(e, sl.h.off, sl.h.cap, n, seg_bytes);
     if (rc != SRTP_OK) return rc;
-    if (!use_tids && (tid < 0 || (size_t)tid >= e->transformers.size()))
-        return fail(e, SRTP_EINVAL, "bad transformer id");
+    rc = check_tid(e, use_tids != 0, tid);
+    if (rc != SRTP_OK) return rc;
     // a small bundle's copies go on the engine's stream: their fixed cost, not
     // their bytes, is its round trip, and two cross-stream events add to it
     const bool one = pl->one_stream || seg_bytes <= kOneStreamBytes;
@@ -2091,7 +2028,7 @@ static int pipeline_submit(srtp_pipeline *pl, int32_t slot, int32_t reverse, int
     const size_t tiny_off = (24ull * n + 15) & ~(size_t)15;
     // direct: k_small reads the block from its pinned host copy and writes
     // the results back there itself -- no copy either way
-    const bool direct = tiny && sl.m_pack && small_path(e, n);
+    const bool direct = tiny && sl.m_pack && bundle_path(engine_shape(e), n) == kPathSmall;
     uint8_t *d_seg = tiny ? reinterpret_cast<uint8_t *>(sl.d_pack) + tiny_off : sl.d_seg;
     if (!tiny) HIPCHK(e, hipMemcpyAsync(sl.d_seg, hseg, seg_bytes, hipMemcpyHostToDevice, si));
     if (n <= kPackMax) {
@@ -2205,9 +2142,8 @@ int srtp_pipeline_submit_gather(srtp_pipeline *pl, int32_t slot, int32_t reverse
     if (!dhost) return fail(e, SRTP_EDEVICE, "registered segment without a device mapping");
     std::lock_guard<std::mutex> g(e->mu);
     int rc = validate_regions(e, sl.h.off, sl.h.cap, n, seg_bytes);
+    if (rc == SRTP_OK) rc = check_tid(e, use_tids != 0, tid);
     if (rc != SRTP_OK) return rc;
-    if (!use_tids && (tid < 0 || (size_t)tid >= e->transformers.size()))
-        return fail(e, SRTP_EINVAL, "bad transformer id");
     const bool one = pl->one_stream;
     hipStream_t s = e->stream, si = one ? s : pl->s_in, so = one ? s : pl->s_out;
     const int32_t abort = abort_on_error < 0 ? -1 : (abort_on_error ? 1 : 0);

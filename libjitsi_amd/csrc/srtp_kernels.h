@@ -4,18 +4,12 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "bundle_plan.h"
 #include "srtp_types.h"
 
 namespace srtp {
 
 constexpr int kSortMaxPass = 4; // 8-bit digits: context tables up to 2^31 slots
-// Context chains of at least this many records in a bundle are walked by the
-// wave-parallel (speculative) walk, shorter ones lane-serially.
-#ifndef SRTP_LONG_MIN
-#define SRTP_LONG_MIN 256
-#endif
-constexpr uint32_t kLongMin = SRTP_LONG_MIN;
-
 // Everything one bundle needs; passed by value to every kernel.
 struct BundleArgs {
     // engine tables (HBM resident)
@@ -101,8 +95,8 @@ struct BundleArgs {
     // selects the walk's GCM instances and the k_gcm passes
     const GcmKeys *gcmkeys;
     int32_t has_gcm;
-    int32_t gcm_route;     // launch_gcm: bits 0-1: 0 by bundle size (kGcmWaveMax), else kGcmRoute* (test hooks);
-                           // kGcmRouteSpec: unprotect in one pass (launch_gcm modes 3 and 4), else verify + decipher
+    int32_t gcm_route;     // BundlePlan::gcm_route (bundle_plan.h): bits 0-1: 0 by bundle size, else kGcmRoute*
+                           // (test hooks); kGcmRouteSpec: unprotect in one pass.  No kernel or launcher reads it.
     const GcmPow *gcmpow;  // [keysets] beside gcmkeys: the powers of H (k_gcm_wave)
 };
 
@@ -117,7 +111,6 @@ struct SortScratch {
     uint32_t *wtotal;               // [2^bits] records per digit
     uint32_t max_tiles;
 };
-constexpr int kSortWideMaxBits = 11;
 
 hipError_t launch_parse(const BundleArgs &a, hipStream_t s);
 size_t sort_temp_bytes(uint32_t n_max);
@@ -137,47 +130,11 @@ hipError_t launch_unprotect(const BundleArgs &a, hipStream_t s);
 // k_unprotect's ROC guess (after k_unprotect, before the walk).  Protect: their
 // trailers (after k_ext).
 hipError_t launch_skein(const BundleArgs &a, hipStream_t s);
-// Engines with AES-GCM key sets (k_gcm).  mode 1 (unprotect, beside k_skein):
-// the tag check under k_unprotect's ROC guess; mode 2 (unprotect, after
-// k_unprotect_fix): the accepted packets deciphered; mode 0 (protect, after
-// k_protect): sealed, tag and SRTCP's E|index word written.
-// A bundle of up to kGcmWaveMax packets takes k_gcm_wave, a wave per packet
-// (the per-packet paths' bundles), a larger one k_gcm, a lane per packet;
-// BundleArgs::gcm_route (SRTP_DEBUG_NO_GCM_WAVE / _FORCE_GCM_WAVE) overrides
-// the size rule.  8192: the largest size of the measured sweep (1 .. 8192
-// 1200-byte packets, profiles/gcm_wave/sweep.json) at which the wave route's
-// median lies below the lane route's by more than the lane route's spread,
-// protect and unprotect; it did at every size of the sweep, by 3.7-4.3x up to
-// 64 packets and by 6-18 % at 8192.
-constexpr uint32_t kGcmWaveMax = 8192u;
-constexpr int32_t kGcmRouteLane = 1, kGcmRouteWave = 2, kGcmRouteMask = 3, kGcmRouteSpec = 4;
-// Unprotect in one pass over the packet bytes (kGcmRouteSpec in BundleArgs::gcm_route,
-// which no kernel reads: the struct every kernel takes by value is the parent's): mode 3
-// (open) in mode 1's place checks the tag under the ROC guess and deciphers in
-// the same trip where gcm_spec_ok (gcm_job.h) allows; mode 4 (fix) in mode 2's
-// place repairs the packets whose verdict the walk overturned (gcm_fix_action)
-// and is otherwise a launch whose workgroups leave at once.  Results are those
-// of modes 1 and 2 to the bit.  It is the default at the sizes of the measured
-// sweep (profiles/gcm_open/sweep.json) at which its median lies below the
-// two-pass route's by more than that route's own p90 - p10, for GCM-128 and
-// GCM-256, on a clean bundle and on one with 2.5 % replays and forgeries:
-//   wave route  4096 and 8192 packets, by 9-11 % clean and 2-5 % with the mix.
-//               Below that a bundle is bound by its launches' latency, and one
-//               packet to repair costs the fix pass what the whole decipher
-//               pass costs: 5-8 % slower at 256 and 1024 with the mix (5-7 %
-//               faster clean there and at 1, 16 and 64).
-//   lane route  nowhere: 2-7 % faster on a clean bundle of 2^18, but 20-36 %
-//               slower with the mix (a wave's 64 lanes wait for the one that
-//               repairs), and 5-73 % slower at 2^14 and 2^16 (one lane's serial
-//               AES + GHASH chain, where two shorter passes overlap better).
-//               Its code is reached by SRTP_DEBUG_FORCE_GCM_SPEC alone.
-// SRTP_DEBUG_NO_GCM_SPEC keeps every bundle on modes 1 and 2, _FORCE_GCM_SPEC
-// puts every bundle of the multi-kernel path on modes 3 and 4.
-constexpr uint32_t kGcmOpenLaneMin = 0x7FFFFFFFu; // no bundle is that large (kRecIdxMask): never
-constexpr uint32_t kGcmOpenWaveMin = 4096u;
-constexpr uint32_t kGcmOpenWaveMax = kGcmWaveMax;
-hipError_t launch_gcm(const BundleArgs &a, int mode, hipStream_t s);
-hipError_t launch_walk(const BundleArgs &a, int limit_pass, hipStream_t s);
+// Engines with AES-GCM key sets: one GcmPass (bundle_plan.h, which also has the
+// size rules), a wave per packet (k_gcm_wave) or a lane per packet (k_gcm) as
+// the bundle's plan says.
+hipError_t launch_gcm(const BundleArgs &a, GcmPass mode, bool wave, hipStream_t s);
+hipError_t launch_walk(const BundleArgs &a, WalkPass pass, hipStream_t s);
 hipError_t launch_protect(const BundleArgs &a, hipStream_t s);
 // BundleArgs::small_ctr: the keystream of the AES-CM + HMAC-SHA1 packets, one
 // workgroup per packet -- protect before k_protect, unprotect after k_unprotect
@@ -188,19 +145,9 @@ hipError_t launch_ctr_small(const BundleArgs &a, hipStream_t s);
 // trailer and final statuses; unprotect: the tag check before the walk)
 hipError_t launch_ctr_wide(const BundleArgs &a, hipStream_t s);
 hipError_t launch_mac_wide(const BundleArgs &a, hipStream_t s);
-// A bundle of up to kSmallMaxN packets (engines whose key sets are all AES-CM
-// or NULL cipher with HMAC-SHA1): parse, sort, (tag check,)
-// walk, keystream and (MAC, trailer) in one workgroup and one launch (k_small).
-constexpr uint32_t kSmallMaxN = 255u;
-// An engine that holds AES-GCM key sets launches k_small's GCM instance, for
-// bundles of up to kSmallGcmMax packets: workgroup 0's eight waves verify the
-// bundle's GCM tags before the walk, a wave per packet, and from two packets
-// per wave on the chain's k_gcm_wave (every packet's wave at once) is faster.
-// The largest size of profiles/gcm_small/sweep.json at which the one-launch
-// route's median lies below the chain's by more than the chain's spread, both
-// ways, for GCM and for AES-CM + HMAC bundles.  SRTP_DEBUG_FORCE_SMALL: up to
-// kSmallMaxN.
-constexpr uint32_t kSmallGcmMax = 8u;
+// A bundle of up to kSmallMaxN packets (kSmallGcmMax once the engine holds
+// AES-GCM key sets; bundle_plan.h): every phase in one workgroup and one launch
+// (k_small).
 hipError_t launch_small(const BundleArgs &a, hipStream_t s);
 // Packet regions [doff[j], + cap[j] rounded to 16) of a device segment from /
 // to [src[j], ...) of device-mapped host memory (a dispatcher shard's gather of

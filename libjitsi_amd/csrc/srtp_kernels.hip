@@ -4937,8 +4937,6 @@ struct GcmPkt {
     int tail_len = 0;
 };
 
-enum { kGcmSeal = 0, kGcmVerify = 1, kGcmDecipher = 2, kGcmOpen = 3, kGcmFix = 4 };
-
 // The whole AEAD for one lane's packet, in one of three modes:
 //   seal      AES-CTR (inc32 from counter 2) over the data in place, GHASH over
 //             AAD || ciphertext || lengths, tag = GHASH ^ E_K(IV || 1);
@@ -5964,9 +5962,7 @@ hipError_t launch_gcm_aead_wave(const GcmBatchWave &g, hipStream_t s) {
     hipLaunchKernelGGL(k_gcm_aead_wave, dim3((g.b.n + per - 1) / per), dim3(kGcmWaveBlock), 0, s, g);
     return hipGetLastError();
 }
-hipError_t launch_gcm(const BundleArgs &a, int mode, hipStream_t s) {
-    const int32_t route = a.gcm_route & kGcmRouteMask;
-    const bool wave = route ? route == kGcmRouteWave : a.n <= kGcmWaveMax;
+hipError_t launch_gcm(const BundleArgs &a, GcmPass mode, bool wave, hipStream_t s) {
     if (wave) { // a wave per packet (the per-packet paths' small bundles)
         const uint32_t per = (uint32_t)(kGcmWaveBlock / 64);
         const dim3 grid((a.n + per - 1) / per), block(kGcmWaveBlock);
@@ -5987,7 +5983,8 @@ hipError_t launch_gcm(const BundleArgs &a, int mode, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_walk(const BundleArgs &a, int limit_pass, hipStream_t s) {
+hipError_t launch_walk(const BundleArgs &a, WalkPass pass, hipStream_t s) {
+    const bool limit_pass = pass == kWalkSecond;
     const uint32_t spans = (a.n + kWalkSpan - 1) / kWalkSpan;
     const dim3 grid(spans);
     if (a.has_gcm) { // engines with AES-GCM key sets: instances of their own (with the Skein re-check)

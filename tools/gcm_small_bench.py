@@ -10,7 +10,7 @@ sweep   protect and unprotect of n 1200-byte GCM-128 SRTP packets (n distinct
         --warmup calls per route first, then --steps timed ones.  Per route the
         median, p10 and p90; `spread` is p90 - p10.  The wave route `wins` at n
         when its median is below the lane route's by more than the lane
-        route's spread, in both directions: kGcmWaveMax (srtp_kernels.h) is
+        route's spread, in both directions: kGcmWaveMax (bundle_plan.h) is
         the largest such n.
 small   the same sweep with the one-launch route (SRTP_DEBUG_FORCE_SMALL: at
         every size up to k_small's 255) against the chain (SRTP_DEBUG_NO_SMALL)
@@ -18,7 +18,7 @@ small   the same sweep with the one-launch route (SRTP_DEBUG_FORCE_SMALL: at
         for AES_CM_128_HMAC_SHA1_80 bundles (--profile gcm,aescm).  The
         one-launch route `wins` at n when its median is below the chain's by
         more than the chain's spread, in both directions: kSmallGcmMax
-        (srtp_kernels.h) is the largest n up to which it wins for both
+        (bundle_plan.h) is the largest n up to which it wins for both
         profiles.
 lone    the per-packet drop-in: p50 / p90 wall time of --calls synchronous
         srtp_aggregator_transform calls from one thread, for a 1200-byte GCM
