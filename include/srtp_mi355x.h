@@ -223,9 +223,10 @@ int srtp_transform_host(srtp_engine *e, int32_t reverse, const int32_t *tids, in
  * min(src_len, src_cap, cap[j]) bytes rounded up to 16 are copied; a source
  * longer than cap[j] ends SRTP_STATUS_DROP_INVALID, a region too small for the
  * trailer SRTP_STATUS_ERR_CAPACITY, by the existing rules (srtp_fanout_job is
- * the rule, on the host).  Nothing of the packet is rewritten per destination
- * (SSRC, sequence number, payload type): the reference's translator rewrites
- * none.
+ * the rule, on the host).  These two entries copy the source byte for byte, as
+ * doWrite does; a bridge whose per-peer send chain rewrites the SSRC, sequence
+ * number, timestamp or payload type in front of SRTP (simulcast, last-N) uses
+ * srtp_fanout_device_rw / srtp_fanout_host_rw below.
  *
  * srtp_fanout_device: every array is a device pointer, the call asynchronous on
  * `stream` like srtp_transform_device, under the engine's lock while it
@@ -278,6 +279,59 @@ typedef struct {
 } srtp_fanout_plan;
 int srtp_fanout_job(int32_t src_idx, int32_t m, int32_t src_len, int32_t src_cap, int32_t src_status,
                     int32_t dst_cap, uint32_t flags, srtp_fanout_plan *out);
+
+/* Fan-out with per-destination rewriting.  In the reference each stream's send
+ * chain holds ptTransformEngine and ssrcRewritingEngine in front of the SRTP
+ * transformer (MediaStreamImpl.java:986-1035): a simulcast or last-N bridge
+ * sends every peer the packet under that peer's target SSRC, with a continuous
+ * sequence number, sometimes a replaced timestamp, and the peer's payload type
+ * (ExtendedSequenceNumberInterval.rewriteRTP, through four RawPacket setters).
+ * The state machine that chooses the values stays on the host; it hands the
+ * device one record per destination entry, values in host byte order, and the
+ * expansion writes them into entry j's copy before the protect chain parses it
+ * -- the SRTP context is found under the rewritten SSRC and the ROC follows the
+ * rewritten sequence number, as for a host-made copy the setters were applied
+ * to.  The rewrite applies to entry j exactly when the entry is not skipped,
+ * rewrite[j].mask & 0xF is non-zero and at least 12 bytes are copied
+ * (min(src_len, src_cap, cap[j]) >= 12); otherwise the copy is what
+ * srtp_fanout_device makes.  The source segment is never written.  Mask bits
+ * above 0xF: srtp_fanout_host_rw refuses them (SRTP_EINVAL, nothing launched);
+ * on the device route, where the records are not read back, they are ignored.
+ * `reserved` is ignored.  The rule knows nothing of the transformer's kind: for
+ * an SRTCP transformer only mask 0 makes sense, which is the caller's
+ * responsibility.  Payload rewriting (RTX, RED, FEC) and RTCP rewriting are not
+ * done here: such a packet goes to its peer as a host-made copy. */
+typedef struct { uint32_t mask, ssrc, timestamp; uint16_t seq; uint8_t pt, reserved; } srtp_fanout_rewrite;
+#define SRTP_REWRITE_SSRC 0x1u       /* RawPacket.setSSRC:           bytes 8..11 = ssrc, big-endian */
+#define SRTP_REWRITE_SEQ 0x2u        /* RawPacket.setSequenceNumber: bytes 2..3  = seq, big-endian */
+#define SRTP_REWRITE_TIMESTAMP 0x4u  /* RawPacket.setTimestamp:      bytes 4..7  = timestamp, big-endian */
+#define SRTP_REWRITE_PT 0x8u         /* RawPacket.setPayloadType:    byte 1 = (byte 1 & 0x80) | (pt & 0x7F) */
+/* srtp_fanout_device / srtp_fanout_host with one more argument after flags:
+ * rewrite, n records (k_fanout_rw).  rewrite == NULL is the call without it,
+ * exactly.  Device route: a device array, 16-byte aligned (else SRTP_EINVAL
+ * before any launch).  Host route: a host array, staged like src_idx. */
+int srtp_fanout_device_rw(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
+                          const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status,
+                          uint32_t m, const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                          const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                          const srtp_fanout_rewrite *rewrite, int32_t *status, uint32_t n, void *stream);
+int srtp_fanout_host_rw(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_bytes, const uint32_t *src_off,
+                        const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status,
+                        uint32_t m, const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                        size_t seg_bytes, const uint32_t *off, uint32_t *len, const uint32_t *cap,
+                        const uint32_t *flags, const srtp_fanout_rewrite *rewrite, int32_t *status, uint32_t n);
+/* The rewrite rule of one destination entry (host only; fanout_job.h, the text
+ * k_fanout_rw compiles): the first seven arguments are srtp_fanout_job's;
+ * words_in are the three little-endian 32-bit words of the copy's header bytes
+ * 0..11.  applies = 1 and words = the patched words when the rewrite applies,
+ * else applies = 0 and words = words_in. */
+typedef struct {
+    int32_t applies;
+    uint32_t words[3];
+} srtp_fanout_rewrite_plan;
+int srtp_fanout_rewrite_job(int32_t src_idx, int32_t m, int32_t src_len, int32_t src_cap, int32_t src_status,
+                            int32_t dst_cap, uint32_t flags, const srtp_fanout_rewrite *rewrite,
+                            const uint32_t *words_in, srtp_fanout_rewrite_plan *out);
 
 /* The engine's own non-blocking stream, created with the engine so that each
  * engine gets a hardware queue of its own (streams created later may share

@@ -9,6 +9,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SRTP_MI355X_LIB: another in-tree build of the same ABI (diagnostic variants)
 LIB_PATH = os.environ.get("SRTP_MI355X_LIB") or os.path.join(_HERE, "libsrtp_mi355x.so")
@@ -89,6 +91,7 @@ EXPORTED = [
     "srtp_gcm_open_wave_max",
     "srtp_gcm_spec_ok", "srtp_gcm_fix_action",
     "srtp_fanout_device", "srtp_fanout_host", "srtp_engine_fanout_stats", "srtp_fanout_job",
+    "srtp_fanout_device_rw", "srtp_fanout_host_rw", "srtp_fanout_rewrite_job",
 ]
 STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 
@@ -188,6 +191,22 @@ class FanoutPlan(C.Structure):
     _fields_ = [("copy_bytes", C.c_int32), ("len_out", C.c_int32), ("flags_out", C.c_uint32),
                 ("by_source", C.c_int32)]
 
+
+class FanoutRewrite(C.Structure):
+    """srtp_fanout_rewrite (include/srtp_mi355x.h): one destination entry's target values, host byte order"""
+    _fields_ = [("mask", C.c_uint32), ("ssrc", C.c_uint32), ("timestamp", C.c_uint32), ("seq", C.c_uint16),
+                ("pt", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+class FanoutRewritePlan(C.Structure):
+    """srtp_fanout_rewrite_plan (include/srtp_mi355x.h)"""
+    _fields_ = [("applies", C.c_int32), ("words", C.c_uint32 * 3)]
+
+
+REWRITE_SSRC, REWRITE_SEQ, REWRITE_TIMESTAMP, REWRITE_PT = 0x1, 0x2, 0x4, 0x8
+# numpy's view of an array of srtp_fanout_rewrite (fanout_host_rw)
+FANOUT_REWRITE_DTYPE = np.dtype([("mask", "<u4"), ("ssrc", "<u4"), ("timestamp", "<u4"), ("seq", "<u2"),
+                                 ("pt", "u1"), ("reserved", "u1")])
 
 DTLS_AEAD = 0x1
 GCM_HDR_THROW = -0x80000000
@@ -331,6 +350,12 @@ def lib() -> C.CDLL:
     L.srtp_fanout_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, i32, vp, vp, vp, vp, vp, vp, u32, vp]
     L.srtp_fanout_host.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, u32, vp, vp, i32, vp, C.c_size_t, vp, vp,
                                    vp, vp, vp, u32]
+    L.srtp_fanout_device_rw.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, u32,
+                                        vp]
+    L.srtp_fanout_host_rw.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, u32, vp, vp, i32, vp, C.c_size_t, vp, vp,
+                                      vp, vp, vp, vp, u32]
+    L.srtp_fanout_rewrite_job.argtypes = [i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutRewrite),
+                                          C.POINTER(C.c_uint32), C.POINTER(FanoutRewritePlan)]
     L.srtp_engine_fanout_stats.argtypes = [vp, C.POINTER(FanoutStats)]
     L.srtp_fanout_job.argtypes = [i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutPlan)]
     L.srtp_trailer_room.argtypes = [i32]

@@ -115,7 +115,8 @@ struct srtp_engine {
     unsigned long long *d_fan_skipped = nullptr;
     uint8_t *hs_seg = nullptr;
     size_t hs_seg_bytes = 0;
-    uint32_t hs_m = 0, hs_n = 0;
+    uint32_t hs_m = 0, hs_n = 0, hs_rw_n = 0;
+    srtp_fanout_rewrite *hs_rw = nullptr; // srtp_fanout_host_rw's records, staged like hs_idx
     uint32_t *hs_off = nullptr, *hs_len = nullptr, *hs_cap = nullptr;
     int32_t *hs_status = nullptr, *hs_idx = nullptr;
     uint64_t fan_calls = 0, fan_sources = 0, fan_destinations = 0, fan_src_bytes = 0;
@@ -614,7 +615,7 @@ void srtp_engine_destroy(srtp_engine *e) {
     void *ptrs[] = {e->d_keysets, e->d_extkeys, e->d_tfkeys, e->d_skkeys, e->d_gcmkeys, e->d_gcmpow, e->d_factories, e->d_transformers, e->d_ctx_keys, e->d_ctx,
                     e->d_far, e->e_min, e->ctl, e->d_count, e->d_counters, e->h_seg, e->h_off, e->h_len,
                     e->h_cap, e->h_flags, e->h_status, e->h_tids, e->fan_flags, e->d_fan_skipped, e->hs_seg,
-                    e->hs_off, e->hs_len, e->hs_cap, e->hs_status, e->hs_idx};
+                    e->hs_off, e->hs_len, e->hs_cap, e->hs_status, e->hs_idx, e->hs_rw};
     for (void *p : ptrs) dfree(p);
     if (e->ev_last) (void)hipEventDestroy(e->ev_last);
     if (e->ev_dev) (void)hipEventDestroy(e->ev_dev);
@@ -1073,8 +1074,11 @@ static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t 
                          const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status, uint32_t m,
                          const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
                          const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
-                         int32_t *status, uint32_t n, hipStream_t s, bool dev_event) {
+                         const srtp_fanout_rewrite *rewrite, int32_t *status, uint32_t n, hipStream_t s,
+                         bool dev_event) {
     int rc = check_fanout(e, {src_seg, src_off, src_len, src_cap, src_idx, seg, off, len, cap, status}, m, n);
+    if (rc == SRTP_OK && ((uintptr_t)rewrite & 15u)) // k_fanout_rw loads a record in one 16-byte piece
+        rc = fail(e, SRTP_EINVAL, "rewrite must be 16-byte aligned");
     if (rc == SRTP_OK) rc = check_tid(e, tids != nullptr, tid);
     if (rc == SRTP_OK) rc = ensure_scratch(e, n);
     if (rc != SRTP_OK) return rc;
@@ -1098,7 +1102,7 @@ static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t 
     f.flags_out = e->fan_flags;
     f.skipped = e->d_fan_skipped;
     f.n = n;
-    HIPCHK(e, launch_fanout(f, s));
+    HIPCHK(e, launch_fanout(f, s, rewrite));
     rc = transform_locked(e, 0, tids, tid, seg, off, len, cap, e->fan_flags, status, n, s, -1, dev_event);
     if (rc != SRTP_OK) return rc;
     e->fan_calls++;
@@ -1107,16 +1111,25 @@ static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t 
     return SRTP_OK;
 }
 
-int srtp_fanout_device(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off, const uint32_t *src_len,
-                       const uint32_t *src_cap, const int32_t *src_status, uint32_t m, const int32_t *src_idx,
-                       const int32_t *tids, int32_t tid, uint8_t *seg, const uint32_t *off, uint32_t *len,
-                       const uint32_t *cap, const uint32_t *flags, int32_t *status, uint32_t n, void *stream) {
+int srtp_fanout_device_rw(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
+                          const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status, uint32_t m,
+                          const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                          const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                          const srtp_fanout_rewrite *rewrite, int32_t *status, uint32_t n, void *stream) {
     if (!e) return SRTP_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     if (n == 0) return SRTP_OK;
     GUARD(e);
     return fanout_locked(e, src_seg, src_off, src_len, src_cap, src_status, m, src_idx, tids, tid, seg, off, len,
-                         cap, flags, status, n, (hipStream_t)stream, true);
+                         cap, flags, rewrite, status, n, (hipStream_t)stream, true);
+}
+
+int srtp_fanout_device(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off, const uint32_t *src_len,
+                       const uint32_t *src_cap, const int32_t *src_status, uint32_t m, const int32_t *src_idx,
+                       const int32_t *tids, int32_t tid, uint8_t *seg, const uint32_t *off, uint32_t *len,
+                       const uint32_t *cap, const uint32_t *flags, int32_t *status, uint32_t n, void *stream) {
+    return srtp_fanout_device_rw(e, src_seg, src_off, src_len, src_cap, src_status, m, src_idx, tids, tid, seg, off,
+                                 len, cap, flags, nullptr, status, n, stream);
 }
 
 int srtp_fanout_host(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_bytes, const uint32_t *src_off,
@@ -1124,6 +1137,15 @@ int srtp_fanout_host(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_byte
                      const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg, size_t seg_bytes,
                      const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
                      int32_t *status, uint32_t n) {
+    return srtp_fanout_host_rw(e, src_seg, src_seg_bytes, src_off, src_len, src_cap, src_status, m, src_idx, tids,
+                               tid, seg, seg_bytes, off, len, cap, flags, nullptr, status, n);
+}
+
+int srtp_fanout_host_rw(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_bytes, const uint32_t *src_off,
+                        const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status, uint32_t m,
+                        const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg, size_t seg_bytes,
+                        const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                        const srtp_fanout_rewrite *rewrite, int32_t *status, uint32_t n) {
     if (!e) return SRTP_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     if (n == 0) return SRTP_OK;
@@ -1133,6 +1155,8 @@ int srtp_fanout_host(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_byte
     if (rc != SRTP_OK) return rc;
     for (uint32_t j = 0; j < n; j++)
         if (src_idx[j] < 0 || (uint32_t)src_idx[j] >= m) return fail(e, SRTP_EINVAL, "src_idx[j] names no source");
+    for (uint32_t j = 0; rewrite && j < n; j++)
+        if (rewrite[j].mask & ~kFanRewriteAll) return fail(e, SRTP_EINVAL, "rewrite[j].mask has a bit above 0xF");
     rc = check_tid(e, tids != nullptr, tid);
     if (rc != SRTP_OK) return rc;
     GUARD(e);
@@ -1140,13 +1164,14 @@ int srtp_fanout_host(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_byte
     rc = ensure_host_staging(e, seg_bytes, n);
     if (rc != SRTP_OK) return rc;
     const size_t need = (src_seg_bytes + 15) & ~(size_t)15;
-    if ((need > e->hs_seg_bytes || m > e->hs_m || n > e->hs_n) && e->have_last) {
+    if ((need > e->hs_seg_bytes || m > e->hs_m || n > e->hs_n || (rewrite && n > e->hs_rw_n)) && e->have_last) {
         rc = quiesce(e); // the source staging may still be read by an enqueued fan-out
         if (rc != SRTP_OK) return rc;
     }
     rc = grow_staging(e, &e->hs_seg_bytes, need, &e->hs_seg);
     if (rc == SRTP_OK) rc = grow_staging(e, &e->hs_m, m, &e->hs_off, &e->hs_len, &e->hs_cap, &e->hs_status);
     if (rc == SRTP_OK) rc = grow_staging(e, &e->hs_n, n, &e->hs_idx);
+    if (rc == SRTP_OK && rewrite) rc = grow_staging(e, &e->hs_rw_n, n, &e->hs_rw);
     if (rc != SRTP_OK) return rc;
     // only the source segment and the small arrays cross to the device
     HIPCHK(e, hipMemcpyAsync(e->hs_seg, src_seg, src_seg_bytes, hipMemcpyHostToDevice, s));
@@ -1155,13 +1180,14 @@ int srtp_fanout_host(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_byte
     HIPCHK(e, hipMemcpyAsync(e->hs_cap, src_cap, m * 4ull, hipMemcpyHostToDevice, s));
     if (src_status) HIPCHK(e, hipMemcpyAsync(e->hs_status, src_status, m * 4ull, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(e->hs_idx, src_idx, n * 4ull, hipMemcpyHostToDevice, s));
+    if (rewrite) HIPCHK(e, hipMemcpyAsync(e->hs_rw, rewrite, n * sizeof *rewrite, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(e->h_off, off, n * 4ull, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(e->h_cap, cap, n * 4ull, hipMemcpyHostToDevice, s));
     if (flags) HIPCHK(e, hipMemcpyAsync(e->h_flags, flags, n * 4ull, hipMemcpyHostToDevice, s));
     if (tids) HIPCHK(e, hipMemcpyAsync(e->h_tids, tids, n * 4ull, hipMemcpyHostToDevice, s));
     rc = fanout_locked(e, e->hs_seg, e->hs_off, e->hs_len, e->hs_cap, src_status ? e->hs_status : nullptr, m,
                        e->hs_idx, tids ? e->h_tids : nullptr, tid, e->h_seg, e->h_off, e->h_len, e->h_cap,
-                       flags ? e->h_flags : nullptr, e->h_status, n, s, false);
+                       flags ? e->h_flags : nullptr, rewrite ? e->hs_rw : nullptr, e->h_status, n, s, false);
     if (rc != SRTP_OK) return rc;
     e->fan_src_bytes += src_seg_bytes;
     HIPCHK(e, hipMemcpyAsync(seg, e->h_seg, seg_bytes, hipMemcpyDeviceToHost, s));
@@ -1199,6 +1225,28 @@ int srtp_fanout_job(int32_t src_idx, int32_t m, int32_t src_len, int32_t src_cap
     out->len_out = j.len_out;
     out->flags_out = j.flags_out;
     out->by_source = j.by_source;
+    return SRTP_OK;
+}
+
+int srtp_fanout_rewrite_job(int32_t src_idx, int32_t m, int32_t src_len, int32_t src_cap, int32_t src_status,
+                            int32_t dst_cap, uint32_t flags, const srtp_fanout_rewrite *rewrite,
+                            const uint32_t *words_in, srtp_fanout_rewrite_plan *out) {
+    if (!rewrite || !words_in || !out) return SRTP_EINVAL;
+    static_assert(sizeof(srtp_fanout_rewrite) == 16 && offsetof(srtp_fanout_rewrite, seq) == 12 &&
+                      offsetof(srtp_fanout_rewrite, pt) == 14,
+                  "k_fanout_rw loads a record as four 32-bit words");
+    static_assert(SRTP_REWRITE_SSRC == kFanRewriteSsrc && SRTP_REWRITE_SEQ == kFanRewriteSeq &&
+                      SRTP_REWRITE_TIMESTAMP == kFanRewriteTimestamp && SRTP_REWRITE_PT == kFanRewritePt,
+                  "fanout_job.h restates these constants");
+    const FanoutJob j = fanout_job(src_idx, m, src_len, src_cap, src_status, dst_cap, flags);
+    out->applies = fanout_rewrite_applies(j, src_len, src_cap, dst_cap, rewrite->mask) ? 1 : 0;
+    FanoutWords w{words_in[0], words_in[1], words_in[2]};
+    if (out->applies)
+        w = fanout_rewrite_words(w.w0, w.w1, w.w2, rewrite->mask, rewrite->ssrc, rewrite->timestamp, rewrite->seq,
+                                 rewrite->pt);
+    out->words[0] = w.w0;
+    out->words[1] = w.w1;
+    out->words[2] = w.w2;
     return SRTP_OK;
 }
 

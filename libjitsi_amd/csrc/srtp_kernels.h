@@ -176,7 +176,10 @@ struct FanoutArgs {
     unsigned long long *skipped;
     uint32_t n;
 };
-hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s);
+// rewrite: null (k_fanout), or n 16-byte records (srtp_fanout_rewrite), 16-byte
+// aligned, in device memory: entry j's copy gets rewrite[j]'s fields where
+// fanout_rewrite_applies says so (k_fanout_rw)
+hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s, const void *rewrite = nullptr);
 // unprotect: statuses/lengths out; undo/redo the rare speculation misses (after the walk)
 hipError_t launch_unprotect_fix(const BundleArgs &a, hipStream_t s);
 // AES-F8 packets after the final statuses: protect (F8 + HMAC + trailer) or

@@ -7104,9 +7104,19 @@ hipError_t launch_move_regions(bool to_device, uint8_t *dseg, const uint32_t *do
 // only an entry with bytes to copy forms a pointer into either segment.  In a
 // source-major bundle the two entries of a wave, and the waves around it,
 // read the same source: its re-reads come from the L2.
+//
+// The rewriting instance (k_fanout_rw, srtp_fanout_*_rw): entry j carries the
+// record rewrite[j] (fanout_job.h).  The first 16-byte piece of a copy is in
+// lane 0's registers between its load and its store; where
+// fanout_rewrite_applies says so for that entry and its own record, its first
+// three words are patched there (fanout_rewrite_words).  The source segment is
+// never written, and an entry without bytes, which borrows its partner's
+// pointers, has no patch: its own record applies to nothing, and the partner's
+// is tied to the partner's piece.
 struct FanEntry {
     FanoutJob job;
     uint32_t src_at; // the source region's offset (copy_bytes > 0 only)
+    int src_len, src_cap, dst_cap; // what the job was asked with (the rewriting instance reads them)
 };
 __device__ __forceinline__ FanEntry fan_entry(const FanoutArgs &f, uint32_t j) {
     const int si = f.src_idx[j];
@@ -7115,12 +7125,31 @@ __device__ __forceinline__ FanEntry fan_entry(const FanoutArgs &f, uint32_t j) {
     const int st = in && f.src_status ? f.src_status[si] : 0;
     const int sl = in ? (int)f.src_len[si] : 0, sc = in ? (int)f.src_cap[si] : 0;
     FanEntry e;
-    e.job = fanout_job(si, (int)f.m, sl, sc, st, (int)f.cap[j], fl);
+    e.src_len = sl;
+    e.src_cap = sc;
+    e.dst_cap = (int)f.cap[j];
+    e.job = fanout_job(si, (int)f.m, sl, sc, st, e.dst_cap, fl);
     e.src_at = e.job.copy_bytes > 0 ? f.src_off[si] : 0u;
     return e;
 }
+// rec: the entry's own record as loaded (mask, ssrc, timestamp, seq | pt << 16 | reserved << 24)
+__device__ __forceinline__ bool fan_patches(const FanEntry &e, const uint4 &rec) {
+    return fanout_rewrite_applies(e.job, e.src_len, e.src_cap, e.dst_cap, rec.x);
+}
+// The piece as it is stored: patched where `patch` holds, else as loaded.  A select on the store's
+// side, so that the loaded registers stay what the loads wrote and every load of a trip is still
+// issued before the first wait.
+__device__ __forceinline__ uint4 fan_patched(const uint4 &piece, const uint4 &rec, bool patch) {
+    const FanoutWords w =
+        fanout_rewrite_words(piece.x, piece.y, piece.z, rec.x, rec.y, rec.z, rec.w & 0xFFFFu, (rec.w >> 16) & 0xFFu);
+    uint4 out = piece;
+    out.x = patch ? w.w0 : piece.x;
+    out.y = patch ? w.w1 : piece.y;
+    out.z = patch ? w.w2 : piece.z;
+    return out;
+}
 
-__global__ __launch_bounds__(kGatherBlock) void k_fanout(FanoutArgs f) {
+template <bool RW> __device__ __forceinline__ void fanout_body(const FanoutArgs &f, const uint4 *rewrite) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t waves = gridDim.x * (kGatherBlock / 64);
     for (uint32_t j = 2u * (blockIdx.x * (kGatherBlock / 64) + (threadIdx.x >> 6)); j < f.n; j += 2u * waves) {
@@ -7144,6 +7173,15 @@ __global__ __launch_bounds__(kGatherBlock) void k_fanout(FanoutArgs f) {
         const uint4 *fb = reinterpret_cast<const uint4 *>(f.src_seg + (wb ? eb.src_at : ea.src_at));
         uint4 *ta = reinterpret_cast<uint4 *>(f.seg + f.off[ja]);
         uint4 *tb = reinterpret_cast<uint4 *>(f.seg + f.off[jb]);
+        // each entry's own record, by its own index (j and j + 1 move with the stride loop)
+        uint4 ra = {}, rb = {};
+        bool pa = false, pb = false;
+        if (RW) {
+            ra = rewrite[j];
+            rb = rewrite[two ? j + 1u : j];
+            pa = fan_patches(ea, ra);
+            pb = two && fan_patches(eb, rb);
+        }
         for (uint32_t o = lane; o < max(wa, wb); o += 128u) {
             const bool a0 = o < wa, a1 = o + 64u < wa, b0 = o < wb, b1 = o + 64u < wb;
             uint4 x0, x1, y0, y1;
@@ -7151,18 +7189,27 @@ __global__ __launch_bounds__(kGatherBlock) void k_fanout(FanoutArgs f) {
             if (a1) x1 = fa[o + 64u];
             if (b0) y0 = fb[o];
             if (b1) y1 = fb[o + 64u];
-            if (a0) ta[o] = x0;
+            // o == 0: lane 0, first trip -- the piece that holds header bytes 0..11
+            if (a0) ta[o] = RW ? fan_patched(x0, ra, pa && o == 0u) : x0;
             if (a1) ta[o + 64u] = x1;
-            if (b0) tb[o] = y0;
+            if (b0) tb[o] = RW ? fan_patched(y0, rb, pb && o == 0u) : y0;
             if (b1) tb[o + 64u] = y1;
         }
     }
 }
 
-hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s) {
+__global__ __launch_bounds__(kGatherBlock) void k_fanout(FanoutArgs f) { fanout_body<false>(f, nullptr); }
+__global__ __launch_bounds__(kGatherBlock) void k_fanout_rw(FanoutArgs f, const uint4 *rewrite) {
+    fanout_body<true>(f, rewrite);
+}
+
+hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s, const void *rewrite) {
     if (f.n == 0) return hipSuccess;
     const uint32_t wgs = std::min<uint32_t>((f.n + 7u) / 8u, 4096u); // two entries per wave
-    hipLaunchKernelGGL(k_fanout, dim3(wgs), dim3(kGatherBlock), 0, s, f);
+    if (rewrite)
+        hipLaunchKernelGGL(k_fanout_rw, dim3(wgs), dim3(kGatherBlock), 0, s, f, static_cast<const uint4 *>(rewrite));
+    else
+        hipLaunchKernelGGL(k_fanout, dim3(wgs), dim3(kGatherBlock), 0, s, f);
     return hipGetLastError();
 }
 

@@ -395,21 +395,38 @@ class SRTPEngine:
         ``src_len`` / ``src_status`` may be the ``length`` / ``status`` tensors
         of a ``transform_device(reverse=True)`` enqueued before on the same
         stream.  Async on ``stream`` like :meth:`transform_device`."""
+        self.fanout_device_rw(tid, src_seg, src_off, src_len, src_cap, src_idx, seg, off, length, cap, status, None,
+                              src_status, flags, m, n, stream)
+
+    def fanout_device_rw(self, tid, src_seg, src_off, src_len, src_cap, src_idx, seg, off, length, cap, status,
+                         rewrite, src_status=None, flags=None, m: Optional[int] = None, n: Optional[int] = None,
+                         stream=None) -> None:
+        """srtp_fanout_device_rw: :meth:`fanout_device` with one rewrite record
+        per destination entry.  ``rewrite`` is a tensor on this engine's GPU
+        that holds n x 16 bytes, 16-byte aligned (n records of
+        ``N.FANOUT_REWRITE_DTYPE``: mask, ssrc, timestamp, seq, pt in host
+        byte order), or None for :meth:`fanout_device` exactly.  Entry j's copy
+        gets the fields its mask names (``N.REWRITE_SSRC`` / ``_SEQ`` /
+        ``_TIMESTAMP`` / ``_PT``) before it is parsed: its SRTP context is the
+        one of the rewritten SSRC.  Mask bits above 0xF are ignored here."""
         if m is None:
             m = src_off.numel()
         if n is None:
             n = off.numel()
+        if rewrite is not None and rewrite.numel() * rewrite.element_size() < 16 * n:
+            raise ValueError("fanout_device_rw: rewrite holds fewer than n records")
         if np.isscalar(tid):
             tids_p, tid0 = None, int(tid)
         else:
             tids_p, tid0 = tid.data_ptr(), -1
         sp = getattr(stream, "cuda_stream", stream)
-        rc = N.lib().srtp_fanout_device(
+        rc = N.lib().srtp_fanout_device_rw(
             self.h, src_seg.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), src_cap.data_ptr(),
             None if src_status is None else src_status.data_ptr(), m, src_idx.data_ptr(), tids_p, tid0,
             seg.data_ptr(), off.data_ptr(), length.data_ptr(), cap.data_ptr(),
-            None if flags is None else flags.data_ptr(), status.data_ptr(), n, sp)
-        N.check(rc, self.h, "srtp_fanout_device")
+            None if flags is None else flags.data_ptr(), None if rewrite is None else rewrite.data_ptr(),
+            status.data_ptr(), n, sp)
+        N.check(rc, self.h, "srtp_fanout_device" if rewrite is None else "srtp_fanout_device_rw")
 
     def fanout_host(self, tid, src_seg: np.ndarray, src_off, src_len, src_cap, src_idx, seg: np.ndarray, off,
                     cap, src_status=None, flags=None):
@@ -418,6 +435,15 @@ class SRTPEngine:
         bytes ``[off[j], off[j] + length[j])`` of the entries with status OK
         are defined, every other byte of it is unspecified.  Returns
         ``(length, status)``."""
+        return self.fanout_host_rw(tid, src_seg, src_off, src_len, src_cap, src_idx, seg, off, cap, src_status, flags,
+                                   None)
+
+    def fanout_host_rw(self, tid, src_seg: np.ndarray, src_off, src_len, src_cap, src_idx, seg: np.ndarray, off,
+                       cap, src_status=None, flags=None, rewrite=None):
+        """srtp_fanout_host_rw: :meth:`fanout_host` with one rewrite record per
+        destination entry, ``rewrite`` a numpy structured array of n records
+        with dtype ``N.FANOUT_REWRITE_DTYPE`` (None: :meth:`fanout_host`
+        exactly).  A mask with a bit above 0xF is refused (SRTP_EINVAL)."""
         assert src_seg.dtype == np.uint8 and src_seg.flags.c_contiguous
         assert seg.dtype == np.uint8 and seg.flags.c_contiguous and seg.flags.writeable
         src_off = np.ascontiguousarray(src_off, np.uint32)
@@ -431,6 +457,8 @@ class SRTPEngine:
         st_in = None if src_status is None else np.ascontiguousarray(src_status, np.int32)
         fl = None if flags is None else np.ascontiguousarray(flags, np.uint32)
         assert (st_in is None or len(st_in) == m) and (fl is None or len(fl) == n)
+        rw = None if rewrite is None else np.ascontiguousarray(rewrite, N.FANOUT_REWRITE_DTYPE)
+        assert rw is None or len(rw) == n
         if np.isscalar(tid):
             tids_p, tid0 = None, int(tid)
         else:
@@ -439,12 +467,12 @@ class SRTPEngine:
             tids_p, tid0 = tids.ctypes.data, -1
         length = np.zeros(n, np.uint32)
         status = np.zeros(n, np.int32)
-        rc = N.lib().srtp_fanout_host(
+        rc = N.lib().srtp_fanout_host_rw(
             self.h, src_seg.ctypes.data, src_seg.nbytes, src_off.ctypes.data, src_len.ctypes.data,
             src_cap.ctypes.data, None if st_in is None else st_in.ctypes.data, m, src_idx.ctypes.data, tids_p,
             tid0, seg.ctypes.data, seg.nbytes, off.ctypes.data, length.ctypes.data, cap.ctypes.data,
-            None if fl is None else fl.ctypes.data, status.ctypes.data, n)
-        N.check(rc, self.h, "srtp_fanout_host")
+            None if fl is None else fl.ctypes.data, None if rw is None else rw.ctypes.data, status.ctypes.data, n)
+        N.check(rc, self.h, "srtp_fanout_host" if rw is None else "srtp_fanout_host_rw")
         return length, status
 
     def fanout_stats(self) -> dict:
@@ -1249,6 +1277,40 @@ def fan_out(pkts: Sequence[Optional[RawPacket]], transformers: Sequence[_SRTPBas
     are written to nobody.  The packets themselves are left as they are.
     Returns one list per transformer: element i is the protected copy of
     packet i as a new RawPacket, or None (not written, dropped, or thrown)."""
+    return _fan_out(pkts, transformers, None, exclusion)
+
+
+def fan_out_rw(pkts: Sequence[Optional[RawPacket]], transformers: Sequence[_SRTPBase], rewriters, exclusion=None):
+    """:func:`fan_out` for a bridge whose per-peer send chain rewrites the
+    packet in front of SRTP.  In the reference each stream's chain holds
+    ptTransformEngine and ssrcRewritingEngine before the SRTP transformer
+    (MediaStreamImpl.java:986-1035), and the rewriting engine gives the copy
+    its target SSRC, sequence number, timestamp and payload type through
+    RawPacket.setSSRC / setSequenceNumber / setTimestamp / setPayloadType
+    (ExtendedSequenceNumberInterval.java:163-229, rewriteRTP).  ``rewriters``
+    holds one rewriter or None per transformer.  A rewriter is a callable
+    ``f(pkt)``; it is called for every copy that would be written toward its
+    transformer (not for a None packet, the excluded stream or a copy the
+    packetPredicate refuses), in doWrite's order: packet by packet and, within
+    a packet, stream by stream -- so a stateful rewriter, such as the
+    reference's, works.  It returns None -- the copy is not written
+    (rewriteRTP returned null) -- or a mapping with any of ``ssrc``, ``seq``,
+    ``timestamp``, ``pt``; an empty mapping leaves the copy unchanged.  The
+    values are written into the copies on the GPU (srtp_fanout_host_rw), and
+    each copy is protected under its rewritten SSRC and sequence number.  The
+    packets themselves are left as they are.  Everything else is
+    :func:`fan_out`'s."""
+    transformers, rewriters = list(transformers), list(rewriters)
+    if len(rewriters) != len(transformers):
+        raise ValueError("fan_out_rw: one rewriter (or None) per transformer")
+    return _fan_out(pkts, transformers, rewriters, exclusion)
+
+
+_REWRITE_FIELDS = (("ssrc", N.REWRITE_SSRC, 0xFFFFFFFF), ("seq", N.REWRITE_SEQ, 0xFFFF),
+                   ("timestamp", N.REWRITE_TIMESTAMP, 0xFFFFFFFF), ("pt", N.REWRITE_PT, 0x7F))
+
+
+def _fan_out(pkts, transformers, rewriters, exclusion):
     pkts, transformers = list(pkts), list(transformers)
     out = [[None] * len(pkts) for _ in transformers]
     if not pkts or not transformers:
@@ -1271,13 +1333,32 @@ def fan_out(pkts: Sequence[Optional[RawPacket]], transformers: Sequence[_SRTPBas
             if x is t or (t.packetPredicate is not None and pkts[i] is not None
                           and not t.packetPredicate(pkts[i])):
                 flags[i * T + k] |= N.PKT_FLAG_SKIP
+    rewrite = None
+    if rewriters is not None and any(f is not None for f in rewriters):
+        rewrite = np.zeros(len(pkts) * T, N.FANOUT_REWRITE_DTYPE)
+        for i, p in enumerate(pkts):  # doWrite's order
+            for k, f in enumerate(rewriters):
+                j = i * T + k
+                if f is None or p is None or flags[j] & N.PKT_FLAG_SKIP:
+                    continue
+                r = f(p)
+                if r is None:
+                    flags[j] |= N.PKT_FLAG_SKIP
+                    continue
+                unknown = set(r) - {name for name, _, _ in _REWRITE_FIELDS}
+                if unknown:
+                    raise ValueError("fan_out_rw: a rewriter returned %s" % sorted(unknown))
+                for name, bit, lim in _REWRITE_FIELDS:
+                    if name in r:
+                        rewrite[name][j] = int(r[name]) & lim
+                        rewrite["mask"][j] |= bit
     step = (cap.astype(np.int64) + 15) & ~15
     off = np.concatenate(([0], np.cumsum(step)[:-1])).astype(np.int64)
     if int(off[-1] + step[-1]) >= 1 << 32:
         raise ValueError("fan_out: more than 4 GiB of copies")
     seg = np.zeros(int(off[-1] + step[-1]), np.uint8)
-    ln, st = eng.fanout_host(tids, src_seg, src_off, src_len, src_cap, src_idx, seg, off.astype(np.uint32), cap,
-                             src_status, flags)
+    ln, st = eng.fanout_host_rw(tids, src_seg, src_off, src_len, src_cap, src_idx, seg, off.astype(np.uint32), cap,
+                                src_status, flags, rewrite)
     for j in np.nonzero(st == N.STATUS_OK)[0]:
         i, k = divmod(int(j), T)
         o = int(off[j])

@@ -12,7 +12,17 @@
             pre-expanded bundle, HIP events; and a plain device copy of the bytes
             k_fanout writes, in the same process.
   --once    three fanout_device calls of the --device shape and nothing else
-            (for a kernel trace of k_fanout in a run of its own).
+            (for a kernel trace of k_fanout in a run of its own); with
+            --rewrite, three fanout_device_rw calls instead (k_fanout_rw).
+  --rewrite per-destination rewriting (srtp_fanout_*_rw), every entry with all
+            four fields set.  Device route, n = 2^18, N = 8: fanout_device_rw
+            against fanout_device, alternating call by call, HIP events.  Host
+            route, 2^16 destinations at N in {1, 4, 16}: fanout_host_rw against
+            what such a bridge does without it -- host expansion with the four
+            setters applied (numpy, one thread, timed) plus transform_host.
+  --plain   fanout_device of the --device shape and nothing else, 5 warm-up and
+            20 timed calls (one side of a comparison between two builds of the
+            library, a process each).
 
 Every call gets sources with new sequence numbers (not timed, for either
 route), so that no destination is a replay.  One JSON document on stdout, or
@@ -65,7 +75,8 @@ class Sources:
         self.advance()
 
     def advance(self):
-        seq = ((self.base + np.arange(self.m) // self.ssrcs) & 0xFFFF).astype(">u2")
+        self.seq = (self.base + np.arange(self.m) // self.ssrcs) & 0xFFFF  # this call's, host order
+        seq = self.seq.astype(">u2")
         self.rows[:, 2:4] = seq.view(np.uint8).reshape(self.m, 2)
         self.base += self.per_call
 
@@ -205,16 +216,168 @@ def device_case(eng, n, fan, once):
             "packets_per_s_pre_expanded": n / (pb["median_ms"] * 1e-3)}
 
 
+REWRITE_DTYPE = np.dtype([("mask", "<u4"), ("ssrc", "<u4"), ("timestamp", "<u4"), ("seq", "<u2"), ("pt", "u1"),
+                          ("reserved", "u1")])  # srtp_fanout_rewrite
+
+
+class Targets:
+    """One record per destination entry with all four fields set: peer k sends
+    source SSRC s on as 0x01000000 * (k + 1) + s, the source's sequence number
+    + 7, a timestamp of its own and payload type 100.  update() follows the
+    sources' new sequence numbers (not timed, for either route: the state
+    machine that chooses the values runs on the host either way)."""
+
+    def __init__(self, src, src_idx, fan):
+        n = len(src_idx)
+        self.src, self.src_idx = src, src_idx
+        self.rw = np.zeros(n, REWRITE_DTYPE)
+        self.rw["mask"] = 0xF
+        peer = np.tile(np.arange(fan, dtype=np.uint32), n // fan)
+        self.rw["ssrc"] = 0x01000000 * (peer + 1) + 0x10000 + src_idx % src.ssrcs
+        self.rw["pt"] = 100
+        self.update()
+
+    def update(self):
+        seq = (self.src.seq[self.src_idx] + 7) & 0xFFFF
+        self.rw["seq"] = seq
+        self.rw["timestamp"] = 0x5A000000 + 960 * seq
+
+    def apply(self, rows):
+        """RawPacket's four setters on the host-made copies (rows: n x stride bytes)."""
+        rows[:, 1] = (rows[:, 1] & 0x80) | (self.rw["pt"] & 0x7F)
+        rows[:, 2:4] = self.rw["seq"].astype(">u2").view(np.uint8).reshape(-1, 2)
+        rows[:, 4:8] = self.rw["timestamp"].astype(">u4").view(np.uint8).reshape(-1, 4)
+        rows[:, 8:12] = self.rw["ssrc"].astype(">u4").view(np.uint8).reshape(-1, 4)
+
+
+def rewrite_host_case(eng, n, fan):
+    profile = "AES_CM_128_HMAC_SHA1_80"
+    m = n // fan
+    ts = peers(eng, profile, fan)
+    hs, hd = HostBuffer(m * SRC_STRIDE), HostBuffer(n * DST_STRIDE)
+    src = Sources(m, hs.array)
+    src_idx = np.repeat(np.arange(m, dtype=np.int32), fan)
+    tids = np.tile(np.array([t.tid for t in ts], np.int32), m)
+    off = (np.arange(n, dtype=np.int64) * DST_STRIDE).astype(np.uint32)
+    cap = np.full(n, DST_CAP, np.uint32)
+    dst_rows = hd.array.reshape(n, DST_STRIDE)
+    tg = Targets(src, src_idx, fan)
+    t_fan, t_old, t_expand = [], [], []
+    for it in range(WARM + TIMED):
+        src.advance()
+        tg.update()
+        t0 = time.perf_counter()
+        ln, st = eng.fanout_host_rw(tids, src.seg, src.off, src.len, src.cap, src_idx, hd.array, off, cap,
+                                    rewrite=tg.rw)
+        t1 = time.perf_counter()
+        assert not st.any() and (ln == LEN + 10).all()
+        assert (dst_rows[:, 8:12] == tg.rw["ssrc"].astype(">u4").view(np.uint8).reshape(-1, 4)).all()
+        src.advance()
+        tg.update()
+        t2 = time.perf_counter()
+        dst_rows[:, :LEN] = src.rows[src_idx]  # the N host-made copies
+        tg.apply(dst_rows)                     # and the send chain's setters on each
+        ln = np.full(n, LEN, np.uint32)
+        t3 = time.perf_counter()
+        st = eng.transform_host(False, tids, hd.array, off, ln, cap)
+        t4 = time.perf_counter()
+        assert not st.any()
+        if it >= WARM:
+            t_fan.append((t1 - t0) * 1e3)
+            t_old.append((t4 - t2) * 1e3)
+            t_expand.append((t3 - t2) * 1e3)
+    for t in ts:
+        t.close()
+    hs.close()
+    hd.close()
+    a, b = pct(t_fan), pct(t_old)
+    return {"profile": profile, "N": fan, "n": n, "m": m, "fanout_host_rw": a,
+            "expand_rewrite_plus_transform_host": b, "host_expansion_and_setters_alone": pct(t_expand),
+            "h2d_bytes_fanout_rw": m * SRC_STRIDE + 3 * 4 * m + 4 * 4 * n + 16 * n,  # ... and the records
+            "h2d_bytes_expand": n * DST_STRIDE + 4 * 4 * n, "verdict": verdict(a, b)}
+
+
+def device_setup(eng, n, fan):
+    import torch
+    m = n // fan
+    ts = peers(eng, "AES_CM_128_HMAC_SHA1_80", fan)
+    src = Sources(m, np.zeros(m * SRC_STRIDE, np.uint8))
+    d = lambda a: torch.from_numpy(a.view(np.int32) if a.dtype == np.uint32 else a).cuda()
+    src_idx = np.repeat(np.arange(m, dtype=np.int32), fan)
+    w = {"m": m, "src": src, "src_idx": src_idx, "d": d,
+         "tids": d(np.tile(np.array([t.tid for t in ts], np.int32), m)),
+         "off": d((np.arange(n, dtype=np.int64) * DST_STRIDE).astype(np.uint32)),
+         "cap": d(np.full(n, DST_CAP, np.uint32)), "s_off": d(src.off), "s_len": d(src.len), "s_cap": d(src.cap),
+         "idx": d(src_idx), "seg": torch.zeros(n * DST_STRIDE, dtype=torch.uint8, device="cuda"),
+         "ln": torch.zeros(n, dtype=torch.int32, device="cuda"), "st": torch.zeros(n, dtype=torch.int32, device="cuda"),
+         "stream": torch.cuda.Stream()}
+    return w
+
+
+def timed_fanout(eng, w, rewrite):
+    """One fan-out of fresh sources on the stream, between two HIP events: ms."""
+    import torch
+    w["src"].advance()
+    s_seg = w["d"](w["src"].seg)
+    rw = None
+    if rewrite is not None:
+        rewrite.update()
+        rw = torch.from_numpy(rewrite.rw.view(np.uint8)).cuda()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    with torch.cuda.stream(w["stream"]):
+        a.record()
+        if rw is None:
+            eng.fanout_device(w["tids"], s_seg, w["s_off"], w["s_len"], w["s_cap"], w["idx"], w["seg"], w["off"],
+                              w["ln"], w["cap"], w["st"], stream=w["stream"])
+        else:
+            eng.fanout_device_rw(w["tids"], s_seg, w["s_off"], w["s_len"], w["s_cap"], w["idx"], w["seg"], w["off"],
+                                 w["ln"], w["cap"], w["st"], rw, stream=w["stream"])
+        b.record()
+    b.synchronize()
+    eng.sync(w["stream"].cuda_stream)
+    assert not w["st"].any().item()
+    return a.elapsed_time(b)
+
+
+def rewrite_device_case(eng, n, fan):
+    w = device_setup(eng, n, fan)
+    tg = Targets(w["src"], w["src_idx"], fan)
+    t_rw, t_plain = [], []
+    for it in range(WARM + TIMED):
+        x = timed_fanout(eng, w, tg)
+        hdr = w["seg"].view(n, DST_STRIDE)[:: max(1, n // 64), 8:12].cpu().numpy()
+        assert (hdr == tg.rw["ssrc"][:: max(1, n // 64)].astype(">u4").view(np.uint8).reshape(-1, 4)).all()
+        y = timed_fanout(eng, w, None)
+        if it >= WARM:
+            t_rw.append(x)
+            t_plain.append(y)
+    a, b = pct(t_rw), pct(t_plain)
+    spread = max(a["p90_ms"] - a["p10_ms"], b["p90_ms"] - b["p10_ms"])
+    return {"n": n, "N": fan, "m": w["m"], "fanout_device_rw_all_four_fields": a, "fanout_device": b,
+            "difference_of_medians_ms": a["median_ms"] - b["median_ms"], "wider_p90_minus_p10_ms": spread,
+            "differ_by_more_than_the_spread": abs(a["median_ms"] - b["median_ms"]) > spread,
+            "record_bytes_read": 16 * n, "bytes_written": n * LEN}
+
+
+def plain_device_case(eng, n, fan):
+    w = device_setup(eng, n, fan)
+    t = [timed_fanout(eng, w, None) for _ in range(WARM + TIMED)][WARM:]
+    return {"n": n, "N": fan, "m": w["m"], "fanout_device": pct(t)}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--host", action="store_true")
     ap.add_argument("--device", action="store_true")
     ap.add_argument("--once", action="store_true")
+    ap.add_argument("--rewrite", action="store_true")
+    ap.add_argument("--plain", action="store_true")
     ap.add_argument("--log2n-host", type=int, default=16)
     ap.add_argument("--log2n-device", type=int, default=18)
     ap.add_argument("--out")
     args = ap.parse_args()
-    if args.device or args.once:
+    if args.device or args.once or args.rewrite or args.plain:
         import torch  # asked before the engine library initialises HIP: torch caches its first answer
         assert torch.cuda.is_available()
     eng = SRTPEngine(device=0, max_contexts=1 << 19, max_factories=256, max_transformers=256,
@@ -224,8 +387,17 @@ def main():
     if args.host:
         res["host"] = [host_case(eng, prof, 1 << args.log2n_host, fan)
                        for prof in ("AES_CM_128_HMAC_SHA1_80", "AEAD_AES_128_GCM") for fan in (1, 2, 4, 8, 16)]
-    if args.device or args.once:
+    if args.once and args.rewrite:  # three fanout_device_rw calls and nothing else (a trace of k_fanout_rw)
+        w = device_setup(eng, 1 << args.log2n_device, 8)
+        tg = Targets(w["src"], w["src_idx"], 8)
+        res["device"] = {"once_rw_ms": [timed_fanout(eng, w, tg) for _ in range(3)]}
+    elif args.device or args.once:
         res["device"] = device_case(eng, 1 << args.log2n_device, 8, args.once)
+    elif args.rewrite:
+        res["rewrite_device"] = rewrite_device_case(eng, 1 << args.log2n_device, 8)
+        res["rewrite_host"] = [rewrite_host_case(eng, 1 << args.log2n_host, fan) for fan in (1, 4, 16)]
+    if args.plain:
+        res["plain_device"] = plain_device_case(eng, 1 << args.log2n_device, 8)
     res["fanout_stats"] = eng.fanout_stats()
     eng.close()
     text = json.dumps(res, indent=1)
