@@ -64,7 +64,7 @@
 extern "C" {
 #endif
 
-#define SRTP_MI355X_ABI_VERSION 3
+#define SRTP_MI355X_ABI_VERSION 4
 
 /* SRTPPolicy constants (transform/srtp/SRTPPolicy.java:29-63) */
 #define SRTP_NULL_ENCRYPTION 0
@@ -332,6 +332,65 @@ typedef struct {
 int srtp_fanout_rewrite_job(int32_t src_idx, int32_t m, int32_t src_len, int32_t src_cap, int32_t src_status,
                             int32_t dst_cap, uint32_t flags, const srtp_fanout_rewrite *rewrite,
                             const uint32_t *words_in, srtp_fanout_rewrite_plan *out);
+
+/* Fan-out that stamps abs-send-time per destination.  The third engine the
+ * reference puts in front of a stream's SRTP transformer is absSendTimeEngine
+ * (MediaStreamImpl.java:1018-1035): AbsSendTimeEngine.replaceAbsSendTime
+ * (AbsSendTimeEngine.java:86-152) walks the packet's one-byte header-extension
+ * elements, and the first element whose ID is the stream's negotiated
+ * abs-send-time ID, if its len field is 2, gets its three data bytes
+ * overwritten with the local send time in 6.18 fixed point.  Those bytes are
+ * authenticated (and AAD under AES-GCM), so they are written into entry j's
+ * copy before the protect chain sees it.  The host hands the device one record
+ * per destination entry: the 24-bit value (the top 8 bits are ignored), the
+ * peer's ID and `on`.  The record is on when on != 0; an id above 15 never
+ * matches (as in the reference, whose ID is an int compared with a nibble) and
+ * behaves as off; `reserved` is ignored.
+ *
+ * With c = min(src_len, src_cap, cap[j]) and b the copy's bytes, the stamp
+ * applies only if the entry is not skipped, the record is on, c >= 12,
+ * (b[0] >> 6) == 2 and b[0] & 0x10.  The walk is the reference's, with a buffer
+ * that ends where the c copied bytes end and Java's signed bytes:
+ *   p = 12 + 4 * (b[0] & 15) + 2
+ *   if p + 1 < c:  lw = (sbyte(b[p]) << 8) | sbyte(b[p + 1]);  nbytes = 4 * (1 + lw)
+ *     p += 2; inner = 0
+ *     while p < c and inner < nbytes:
+ *       if (b[p] >> 4) == id:  stamp b[p + 1 .. p + 3] if (b[p] & 15) == 2 and p + 3 < c;  stop
+ *       inner += (b[p] & 15) + 2;  p += (b[p] & 15) + 2
+ * with what follows from it: a length field with a byte >= 0x80 walks nothing;
+ * the "defined by profile" word is not looked at; the walk may step four bytes
+ * past the extension and stamp there; a padding byte advances by 2; the first
+ * element with the ID ends the walk whatever its len.  Every stamped byte is
+ * one the copy wrote; the source segment is never written.  Nothing is
+ * inserted: a packet without the element leaves as it came.  The rewrite
+ * records touch bytes 1..11 and the walk reads b[0] of them only, so the two
+ * apply in either order. */
+typedef struct { uint32_t value; uint8_t id, on; uint16_t reserved; } srtp_fanout_abs_send_time;
+/* srtp_fanout_device_rw / srtp_fanout_host_rw with one more argument after
+ * rewrite: stamp, n records (k_fanout_ast).  stamp == NULL is the _rw call,
+ * exactly.  With stamp set, rewrite may be NULL (stamp only) or set (both).
+ * Device route: a device array, 8-byte aligned (else SRTP_EINVAL before any
+ * launch).  Host route: a host array, staged like src_idx and rewrite. */
+int srtp_fanout_device_ast(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
+                           const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status,
+                           uint32_t m, const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                           const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                           const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
+                           int32_t *status, uint32_t n, void *stream);
+int srtp_fanout_host_ast(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_bytes, const uint32_t *src_off,
+                         const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status,
+                         uint32_t m, const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                         size_t seg_bytes, const uint32_t *off, uint32_t *len, const uint32_t *cap,
+                         const uint32_t *flags, const srtp_fanout_rewrite *rewrite,
+                         const srtp_fanout_abs_send_time *stamp, int32_t *status, uint32_t n);
+/* The stamp rule of one destination entry (host only; fanout_job.h, the text
+ * k_fanout_ast compiles) over the caller's bytes: pkt[0 .. bound) is the
+ * packet (reads past bound, which cannot happen for bound >= min(src_len,
+ * src_cap, dst_cap), answer 0); the next seven arguments are srtp_fanout_job's.
+ * *out = the offset of the first of the three stamped bytes, or -1. */
+int srtp_fanout_ast_job(const uint8_t *pkt, uint32_t bound, int32_t src_idx, int32_t m, int32_t src_len,
+                        int32_t src_cap, int32_t src_status, int32_t dst_cap, uint32_t flags,
+                        const srtp_fanout_abs_send_time *stamp, int32_t *out);
 
 /* The engine's own non-blocking stream, created with the engine so that each
  * engine gets a hardware queue of its own (streams created later may share

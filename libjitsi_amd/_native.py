@@ -40,7 +40,7 @@ DEBUG_NO_GCM_SPEC = 0x80     # GCM unprotect always in two passes (tag check, wa
 DEBUG_FORCE_GCM_SPEC = 0x100  # ... always in one (k_gcm<open> / <fix>), on the multi-kernel path
 GCM_FIX_NONE, GCM_FIX_RESTORE, GCM_FIX_DECIPHER = 0, 1, 2  # srtp_gcm_fix_action (bits)
 GCM_BATCH_WAVE = 0x1         # srtp_aes_gcm_device_ex: a wave per packet
-ABI_VERSION = 3
+ABI_VERSION = 4
 AGG_SEAL_IDLE = 0x1
 PKT_FLAG_DISCARD, PKT_FLAG_SILENCE, PKT_FLAG_SKIP = 0x2, 0x4, 0x80000000
 RC = {0: "SRTP_OK", -1: "SRTP_EINVAL", -2: "SRTP_ENOMEM", -3: "SRTP_EFULL", -4: "SRTP_EDEVICE",
@@ -92,6 +92,7 @@ EXPORTED = [
     "srtp_gcm_spec_ok", "srtp_gcm_fix_action",
     "srtp_fanout_device", "srtp_fanout_host", "srtp_engine_fanout_stats", "srtp_fanout_job",
     "srtp_fanout_device_rw", "srtp_fanout_host_rw", "srtp_fanout_rewrite_job",
+    "srtp_fanout_device_ast", "srtp_fanout_host_ast", "srtp_fanout_ast_job",
 ]
 STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 
@@ -207,6 +208,16 @@ REWRITE_SSRC, REWRITE_SEQ, REWRITE_TIMESTAMP, REWRITE_PT = 0x1, 0x2, 0x4, 0x8
 # numpy's view of an array of srtp_fanout_rewrite (fanout_host_rw)
 FANOUT_REWRITE_DTYPE = np.dtype([("mask", "<u4"), ("ssrc", "<u4"), ("timestamp", "<u4"), ("seq", "<u2"),
                                  ("pt", "u1"), ("reserved", "u1")])
+
+
+
+class FanoutAbsSendTime(C.Structure):
+    """srtp_fanout_abs_send_time (include/srtp_mi355x.h): one destination entry's abs-send-time stamp"""
+    _fields_ = [("value", C.c_uint32), ("id", C.c_uint8), ("on", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+# numpy's view of an array of srtp_fanout_abs_send_time (fanout_host_ast)
+FANOUT_AST_DTYPE = np.dtype([("value", "<u4"), ("id", "u1"), ("on", "u1"), ("reserved", "<u2")])
 
 DTLS_AEAD = 0x1
 GCM_HDR_THROW = -0x80000000
@@ -356,6 +367,12 @@ def lib() -> C.CDLL:
                                       vp, vp, vp, vp, u32]
     L.srtp_fanout_rewrite_job.argtypes = [i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutRewrite),
                                           C.POINTER(C.c_uint32), C.POINTER(FanoutRewritePlan)]
+    L.srtp_fanout_device_ast.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                         u32, vp]
+    L.srtp_fanout_host_ast.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, u32, vp, vp, i32, vp, C.c_size_t, vp, vp,
+                                       vp, vp, vp, vp, vp, u32]
+    L.srtp_fanout_ast_job.argtypes = [vp, u32, i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutAbsSendTime),
+                                      C.POINTER(C.c_int32)]
     L.srtp_engine_fanout_stats.argtypes = [vp, C.POINTER(FanoutStats)]
     L.srtp_fanout_job.argtypes = [i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutPlan)]
     L.srtp_trailer_room.argtypes = [i32]

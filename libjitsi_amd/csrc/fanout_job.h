@@ -49,6 +49,45 @@
 // nothing about the transformer's kind: it writes the bytes the four setters
 // write, as RawPacket does.  For an SRTCP transformer only mask 0 makes sense
 // (bytes 4..7 are its SSRC); that is the caller's responsibility.
+//
+// Abs-send-time (srtp_fanout_device_ast / _host_ast): entry j may also carry an
+// 8-byte record (value, id, on) for the third engine of the peer's send chain,
+// AbsSendTimeEngine (AbsSendTimeEngine.java:46-152), which overwrites the three
+// data bytes of the copy's abs-send-time header-extension element.  Where those
+// bytes lie is found by a walk over the packet's own bytes, so the rule is
+// templated on a byte reader (rd(i): byte i of the packet, 0..255); no pointer
+// enters it.  Compiled alike by the host (srtp_fanout_ast_job,
+// tools/fanout_ast_check.cpp) and by k_fanout_ast:
+//   fanout_ast_wanted  c = min(src_len, src_cap, dst_cap), clamped as above,
+//             when the entry is not skipped, the record is on (on != 0), its id
+//             is at most 15 (the reference compares an int with a nibble: a
+//             larger one never matches) and c >= 12; else 0.  Asked before any
+//             byte is read: 0 means no walk.
+//   fanout_ast_find    the offset of the first stamped byte, or -1: the
+//             reference's transform / replaceAbsSendTime over a buffer that
+//             ends with the c copied bytes (buf.length = c), Java's integer
+//             semantics included.  (b[0] >> 6) == 2 and b[0] & 0x10, then
+//               p = 12 + 4 * (b[0] & 15) + 2; only if p + 1 < c:
+//               lw = sbyte(b[p]) << 8 | sbyte(b[p + 1]); nbytes = 4 * (1 + lw)
+//               p += 2; while p < c and inner < nbytes: the element b[p]; the
+//               first whose id matches ends the walk, stamped at p + 1 .. p + 3
+//               if its len is 2 and p + 3 < c; else inner, p += len + 2.
+//             The reference's quirks are kept: a length byte >= 0x80 makes lw
+//             negative (nothing is walked); the "defined by profile" word is
+//             not looked at; nbytes counts four bytes too many, and a match
+//             there is stamped, into the payload; a padding byte advances by
+//             2, and with id 0 is a match of len 0; the first match decides.
+//             rd is asked only for 0 <= i < c, and p + 3 < c: every stamped
+//             byte is one the copy wrote.
+//   fanout_ast_piece   the 16-byte piece q of the copy (four little-endian
+//             words) with whichever of the bytes at .. at + 2 lie in it
+//             replaced by fanout_ast_bytes(value) = value >> 16, >> 8, >> 0
+//             (the top 8 bits of value are ignored), every other byte
+//             untouched: a stamp that straddles two pieces is two calls.
+//             Selects only, no branch.
+// The four setters touch bytes 1..11 and the walk reads b[0] of the fixed header
+// only, which no setter writes; the stamp lies at byte 17 or later.  So the two
+// rules are independent of the order they are applied in.
 #pragma once
 #include <stdint.h>
 
@@ -137,6 +176,89 @@ SRTP_FANOUT_HD inline FanoutWords fanout_rewrite_words(uint32_t w0, uint32_t w1,
     if (mask & kFanRewriteTimestamp) w.w1 = fanout_be32(timestamp);
     if (mask & kFanRewriteSsrc) w.w2 = fanout_be32(ssrc);
     return w;
+}
+
+// ---- abs-send-time (srtp_fanout_device_ast / _host_ast, k_fanout_ast)
+
+// c = min(src_len, src_cap, dst_cap) clamped as above when entry j's record can stamp at all --
+// the entry is not skipped, the record is on, its ID fits a nibble and the fixed header was
+// copied -- else 0.  Asked before any byte of the packet is read: 0 means no walk.
+SRTP_FANOUT_HD inline int fanout_ast_wanted(const FanoutJob &j, int src_len, int src_cap, int dst_cap, uint32_t on,
+                                            uint32_t ext_id) {
+    if ((j.flags_out & kFanFlagSkip) || on == 0u || ext_id > 15u) return 0;
+    if (src_len < 0 || src_cap < 0 || dst_cap < 0) return 0;
+    int c = fanout_clamp(src_len);
+    const int sc = fanout_clamp(src_cap), dc = fanout_clamp(dst_cap);
+    if (c > sc) c = sc;
+    if (c > dc) c = dc;
+    return c >= kFanHeaderBytes && j.copy_bytes >= c ? c : 0; // every byte below c is one the copy writes
+}
+
+SRTP_FANOUT_HD inline int fanout_sbyte(int b) { return b >= 128 ? b - 256 : b; } // a Java byte
+
+// The offset of the first of the three bytes AbsSendTimeEngine would overwrite, or -1.  rd(i)
+// is byte i of the packet and is asked only for 0 <= i < c.
+template <class Rd>
+SRTP_FANOUT_HD inline int fanout_ast_find(Rd rd, const FanoutJob &j, int src_len, int src_cap, int dst_cap,
+                                          uint32_t on, uint32_t ext_id) {
+    const int B = fanout_ast_wanted(j, src_len, src_cap, dst_cap, on, ext_id);
+    if (B == 0) return -1;
+    const int b0 = rd(0);
+    if ((b0 >> 6) != 2 || (b0 & 0x10) == 0) return -1; // getVersion() == 2 && getExtensionBit()
+    int p = kFanHeaderBytes + 4 * (b0 & 15) + 2;       // behind the CSRCs and "defined by profile"
+    if (!(p + 1 < B)) return -1;
+    const int lw = (fanout_sbyte(rd(p)) * 256) | fanout_sbyte(rd(p + 1)); // buf[p] << 8 | buf[p + 1], signed bytes
+    const int nbytes = 4 * (1 + lw);
+    p += 2;
+    int inner = 0;
+    while (p < B && inner < nbytes) {
+        const int e = rd(p);
+        const int len = e & 15;
+        if ((e >> 4) == (int)ext_id) return len == 2 && p + 3 < B ? p + 1 : -1;
+        inner += len + 2;
+        p += len + 2;
+    }
+    return -1;
+}
+
+struct FanoutBytes {
+    uint32_t b0, b1, b2; // in the packet's order
+};
+SRTP_FANOUT_HD inline FanoutBytes fanout_ast_bytes(uint32_t value) {
+    FanoutBytes b;
+    b.b0 = (value >> 16) & 0xFFu;
+    b.b1 = (value >> 8) & 0xFFu;
+    b.b2 = value & 0xFFu;
+    return b;
+}
+
+struct FanoutPiece {
+    uint32_t w0, w1, w2, w3; // bytes 16q .. 16q + 15 of the copy, loaded little-endian
+};
+
+// One word of a piece: `s` is where the stamp starts relative to the word's first byte.
+// Without a branch (selects only: in the kernel this sits between a trip's loads and its stores):
+// for s in -2 .. 3 the three bytes, two bytes in front of the word, are moved s + 2 bytes up and
+// the word's four are kept.
+SRTP_FANOUT_HD inline uint32_t fanout_ast_word(uint32_t w, int s, uint32_t v) {
+    const bool in = s >= -2 && s <= 3;
+    const int up = in ? 8 * (s + 2) : 0; // 0 .. 40
+    const uint32_t m = (uint32_t)(((uint64_t)0x00FFFFFFu << up) >> 16);
+    const uint32_t x = (uint32_t)(((uint64_t)v << up) >> 16);
+    return in ? (w & ~m) | x : w;
+}
+
+// Piece q with whichever of the bytes at .. at + 2 lie in it replaced (at >= 0).
+SRTP_FANOUT_HD inline FanoutPiece fanout_ast_piece(const FanoutPiece &piece, int q, int at, uint32_t value) {
+    const FanoutBytes b = fanout_ast_bytes(value);
+    const uint32_t v = b.b0 | (b.b1 << 8) | (b.b2 << 16); // the three bytes as memory holds them
+    const int s = at - 16 * q;
+    FanoutPiece o;
+    o.w0 = fanout_ast_word(piece.w0, s, v);
+    o.w1 = fanout_ast_word(piece.w1, s - 4, v);
+    o.w2 = fanout_ast_word(piece.w2, s - 8, v);
+    o.w3 = fanout_ast_word(piece.w3, s - 12, v);
+    return o;
 }
 
 } // namespace srtp

@@ -7203,10 +7203,125 @@ __global__ __launch_bounds__(kGatherBlock) void k_fanout_rw(FanoutArgs f, const 
     fanout_body<true>(f, rewrite);
 }
 
-hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s, const void *rewrite) {
+// The stamping instance (k_fanout_ast, srtp_fanout_*_ast): entry j carries the
+// record stamp[j] (value, id | on << 8) and, where `rewrite` is given,
+// rewrite[j] as above.  Before the copy loop the wave finds where each of its
+// two entries is stamped: fanout_ast_wanted decides from the job and the
+// entry's own record whether it walks at all; 16 lanes per entry park the
+// source's first 256 bytes (the lines the copy loop reads next) in the wave's
+// LDS row, and lanes 0 and 1 run fanout_ast_find over entry a's and entry b's
+// half -- past the row, a pathological extension, it reads the source region
+// byte by byte, below c.  The offsets are broadcast; the copy loop is
+// k_fanout_rw's with every stored piece passed through fanout_ast_piece where
+// it holds one of the three bytes, again a select on the store's side.  The
+// row is the wave's own: the hand-offs are walk_sync's, reached by every lane
+// whenever the wave has an entry that walks (a wave-uniform condition).
+constexpr uint32_t kFanAstLanes = 16;                    // lanes that stage one entry's prefix
+constexpr uint32_t kFanAstPrefix = 16u * kFanAstLanes;   // bytes of it
+struct FanAstReader {
+    const uint8_t *row; // LDS: the first `staged` bytes of the source
+    const uint8_t *src; // the source region
+    int staged;
+    __device__ __forceinline__ int operator()(int i) const { return i < staged ? row[i] : src[i]; }
+};
+// rec: the entry's own record as loaded (value, id | on << 8 | reserved << 16)
+__device__ __forceinline__ int fan_ast_wanted(const FanEntry &e, const uint2 &rec) {
+    return fanout_ast_wanted(e.job, e.src_len, e.src_cap, e.dst_cap, (rec.y >> 8) & 0xFFu, rec.y & 0xFFu);
+}
+// Piece q as it is stored: stamped where it holds one of the bytes at .. at + 2, else as given.
+__device__ __forceinline__ uint4 fan_stamped(const uint4 &piece, uint32_t q, int at, uint32_t value) {
+    const bool hit = at >= 0 && (int)q >= (at >> 4) && (int)q <= ((at + 2) >> 4);
+    const FanoutPiece p = fanout_ast_piece(FanoutPiece{piece.x, piece.y, piece.z, piece.w}, (int)q, at, value);
+    uint4 out;
+    out.x = hit ? p.w0 : piece.x;
+    out.y = hit ? p.w1 : piece.y;
+    out.z = hit ? p.w2 : piece.z;
+    out.w = hit ? p.w3 : piece.w;
+    return out;
+}
+
+__global__ __launch_bounds__(kGatherBlock) void k_fanout_ast(FanoutArgs f, const uint4 *rewrite, const uint2 *stamp) {
+    __shared__ uint4 rows[kGatherBlock / 64][2u * kFanAstLanes];
+    const uint32_t lane = threadIdx.x & 63u;
+    uint4 *row = rows[threadIdx.x >> 6];
+    const uint32_t waves = gridDim.x * (kGatherBlock / 64);
+    for (uint32_t j = 2u * (blockIdx.x * (kGatherBlock / 64) + (threadIdx.x >> 6)); j < f.n; j += 2u * waves) {
+        const bool two = j + 1u < f.n;
+        const FanEntry ea = fan_entry(f, j), eb = fan_entry(f, two ? j + 1u : j);
+        if (lane == 0u) {
+            f.len[j] = (uint32_t)ea.job.len_out;
+            f.flags_out[j] = ea.job.flags_out;
+            if (two) {
+                f.len[j + 1u] = (uint32_t)eb.job.len_out;
+                f.flags_out[j + 1u] = eb.job.flags_out;
+            }
+            const unsigned long long sk = (unsigned long long)(ea.job.by_source + (two ? eb.job.by_source : 0));
+            if (sk) atomicAdd(f.skipped, sk);
+        }
+        const uint32_t wa = (uint32_t)ea.job.copy_bytes / 16u, wb = two ? (uint32_t)eb.job.copy_bytes / 16u : 0u;
+        if ((wa | wb) == 0u) continue; // no work: no pointer is formed
+        const uint32_t ja = wa ? j : j + 1u, jb = wb ? j + 1u : j;
+        const uint4 *fa = reinterpret_cast<const uint4 *>(f.src_seg + (wa ? ea.src_at : eb.src_at));
+        const uint4 *fb = reinterpret_cast<const uint4 *>(f.src_seg + (wb ? eb.src_at : ea.src_at));
+        uint4 *ta = reinterpret_cast<uint4 *>(f.seg + f.off[ja]);
+        uint4 *tb = reinterpret_cast<uint4 *>(f.seg + f.off[jb]);
+        // each entry's own records, by its own index
+        uint4 ra = {}, rb = {};
+        bool pa = false, pb = false;
+        if (rewrite) {
+            ra = rewrite[j];
+            rb = rewrite[two ? j + 1u : j];
+            pa = fan_patches(ea, ra);
+            pb = two && fan_patches(eb, rb);
+        }
+        const uint2 sa = stamp[j], sb = stamp[two ? j + 1u : j];
+        // an entry without bytes, or a second entry that is not there, wants nothing
+        const int ca = wa ? fan_ast_wanted(ea, sa) : 0, cb = wb ? fan_ast_wanted(eb, sb) : 0;
+        int ata = -1, atb = -1;
+        if ((ca | cb) != 0) { // the same for every lane of the wave
+            walk_sync();      // the previous pair's walk has read the row
+            const uint32_t piece = lane & (kFanAstLanes - 1u);
+            if (lane < kFanAstLanes) {
+                if (ca && piece < wa) row[lane] = fa[piece];
+            } else if (lane < 2u * kFanAstLanes) {
+                if (cb && piece < wb) row[lane] = fb[piece];
+            }
+            walk_sync();
+            int at = -1;
+            if (lane == 0u && ca) {
+                const FanAstReader rd{reinterpret_cast<const uint8_t *>(row), reinterpret_cast<const uint8_t *>(fa),
+                                      (int)min(kFanAstPrefix, 16u * wa)};
+                at = fanout_ast_find(rd, ea.job, ea.src_len, ea.src_cap, ea.dst_cap, (sa.y >> 8) & 0xFFu, sa.y & 0xFFu);
+            } else if (lane == 1u && cb) {
+                const FanAstReader rd{reinterpret_cast<const uint8_t *>(row + kFanAstLanes),
+                                      reinterpret_cast<const uint8_t *>(fb), (int)min(kFanAstPrefix, 16u * wb)};
+                at = fanout_ast_find(rd, eb.job, eb.src_len, eb.src_cap, eb.dst_cap, (sb.y >> 8) & 0xFFu, sb.y & 0xFFu);
+            }
+            ata = __builtin_amdgcn_readlane(at, 0);
+            atb = __builtin_amdgcn_readlane(at, 1);
+        }
+        for (uint32_t o = lane; o < max(wa, wb); o += 128u) {
+            const bool a0 = o < wa, a1 = o + 64u < wa, b0 = o < wb, b1 = o + 64u < wb;
+            uint4 x0, x1, y0, y1;
+            if (a0) x0 = fa[o];
+            if (a1) x1 = fa[o + 64u];
+            if (b0) y0 = fb[o];
+            if (b1) y1 = fb[o + 64u];
+            if (a0) ta[o] = fan_stamped(fan_patched(x0, ra, pa && o == 0u), o, ata, sa.x);
+            if (a1) ta[o + 64u] = fan_stamped(x1, o + 64u, ata, sa.x);
+            if (b0) tb[o] = fan_stamped(fan_patched(y0, rb, pb && o == 0u), o, atb, sb.x);
+            if (b1) tb[o + 64u] = fan_stamped(y1, o + 64u, atb, sb.x);
+        }
+    }
+}
+
+hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s, const void *rewrite, const void *stamp) {
     if (f.n == 0) return hipSuccess;
     const uint32_t wgs = std::min<uint32_t>((f.n + 7u) / 8u, 4096u); // two entries per wave
-    if (rewrite)
+    if (stamp)
+        hipLaunchKernelGGL(k_fanout_ast, dim3(wgs), dim3(kGatherBlock), 0, s, f, static_cast<const uint4 *>(rewrite),
+                           static_cast<const uint2 *>(stamp));
+    else if (rewrite)
         hipLaunchKernelGGL(k_fanout_rw, dim3(wgs), dim3(kGatherBlock), 0, s, f, static_cast<const uint4 *>(rewrite));
     else
         hipLaunchKernelGGL(k_fanout, dim3(wgs), dim3(kGatherBlock), 0, s, f);

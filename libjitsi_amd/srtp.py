@@ -428,6 +428,41 @@ class SRTPEngine:
             status.data_ptr(), n, sp)
         N.check(rc, self.h, "srtp_fanout_device" if rewrite is None else "srtp_fanout_device_rw")
 
+    def fanout_device_ast(self, tid, src_seg, src_off, src_len, src_cap, src_idx, seg, off, length, cap, status,
+                          rewrite, stamp, src_status=None, flags=None, m: Optional[int] = None,
+                          n: Optional[int] = None, stream=None) -> None:
+        """srtp_fanout_device_ast: :meth:`fanout_device_rw` with one
+        abs-send-time record per destination entry.  ``stamp`` is a tensor on
+        this engine's GPU that holds n x 8 bytes, 8-byte aligned (n records of
+        ``N.FANOUT_AST_DTYPE``: value, id, on), or None for
+        :meth:`fanout_device_rw` exactly; ``rewrite`` may be None either way.
+        Where entry j's record is on and its copy carries a one-byte
+        header-extension element with that ID and len 2, found as
+        AbsSendTimeEngine.replaceAbsSendTime finds it
+        (AbsSendTimeEngine.java:86-152; the engine sits in front of SRTP,
+        MediaStreamImpl.java:1018-1035), the element's three bytes become the
+        low 24 bits of ``value``, big-endian, before the copy is protected."""
+        if m is None:
+            m = src_off.numel()
+        if n is None:
+            n = off.numel()
+        if rewrite is not None and rewrite.numel() * rewrite.element_size() < 16 * n:
+            raise ValueError("fanout_device_ast: rewrite holds fewer than n records")
+        if stamp is not None and stamp.numel() * stamp.element_size() < 8 * n:
+            raise ValueError("fanout_device_ast: stamp holds fewer than n records")
+        if np.isscalar(tid):
+            tids_p, tid0 = None, int(tid)
+        else:
+            tids_p, tid0 = tid.data_ptr(), -1
+        sp = getattr(stream, "cuda_stream", stream)
+        rc = N.lib().srtp_fanout_device_ast(
+            self.h, src_seg.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), src_cap.data_ptr(),
+            None if src_status is None else src_status.data_ptr(), m, src_idx.data_ptr(), tids_p, tid0,
+            seg.data_ptr(), off.data_ptr(), length.data_ptr(), cap.data_ptr(),
+            None if flags is None else flags.data_ptr(), None if rewrite is None else rewrite.data_ptr(),
+            None if stamp is None else stamp.data_ptr(), status.data_ptr(), n, sp)
+        N.check(rc, self.h, "srtp_fanout_device_ast")
+
     def fanout_host(self, tid, src_seg: np.ndarray, src_off, src_len, src_cap, src_idx, seg: np.ndarray, off,
                     cap, src_status=None, flags=None):
         """srtp_fanout_host over numpy: only the source segment and the small
@@ -473,6 +508,50 @@ class SRTPEngine:
             tid0, seg.ctypes.data, seg.nbytes, off.ctypes.data, length.ctypes.data, cap.ctypes.data,
             None if fl is None else fl.ctypes.data, None if rw is None else rw.ctypes.data, status.ctypes.data, n)
         N.check(rc, self.h, "srtp_fanout_host" if rw is None else "srtp_fanout_host_rw")
+        return length, status
+
+    def fanout_host_ast(self, tid, src_seg: np.ndarray, src_off, src_len, src_cap, src_idx, seg: np.ndarray, off,
+                        cap, src_status=None, flags=None, rewrite=None, stamp=None):
+        """srtp_fanout_host_ast: :meth:`fanout_host_rw` with one abs-send-time
+        record per destination entry, ``stamp`` a numpy structured array of n
+        records with dtype ``N.FANOUT_AST_DTYPE`` (None:
+        :meth:`fanout_host_rw` exactly).  What a record does is
+        :meth:`fanout_device_ast`'s (AbsSendTimeEngine.java:86-152,
+        MediaStreamImpl.java:1018-1035)."""
+        if stamp is None:
+            return self.fanout_host_rw(tid, src_seg, src_off, src_len, src_cap, src_idx, seg, off, cap, src_status,
+                                       flags, rewrite)
+        assert src_seg.dtype == np.uint8 and src_seg.flags.c_contiguous
+        assert seg.dtype == np.uint8 and seg.flags.c_contiguous and seg.flags.writeable
+        src_off = np.ascontiguousarray(src_off, np.uint32)
+        src_len = np.ascontiguousarray(src_len, np.uint32)
+        src_cap = np.ascontiguousarray(src_cap, np.uint32)
+        src_idx = np.ascontiguousarray(src_idx, np.int32)
+        off = np.ascontiguousarray(off, np.uint32)
+        cap = np.ascontiguousarray(cap, np.uint32)
+        m, n = len(src_off), len(off)
+        assert len(src_len) == m and len(src_cap) == m and len(src_idx) == n and len(cap) == n
+        st_in = None if src_status is None else np.ascontiguousarray(src_status, np.int32)
+        fl = None if flags is None else np.ascontiguousarray(flags, np.uint32)
+        assert (st_in is None or len(st_in) == m) and (fl is None or len(fl) == n)
+        rw = None if rewrite is None else np.ascontiguousarray(rewrite, N.FANOUT_REWRITE_DTYPE)
+        ast = np.ascontiguousarray(stamp, N.FANOUT_AST_DTYPE)
+        assert (rw is None or len(rw) == n) and len(ast) == n
+        if np.isscalar(tid):
+            tids_p, tid0 = None, int(tid)
+        else:
+            tids = np.ascontiguousarray(tid, np.int32)
+            assert len(tids) == n
+            tids_p, tid0 = tids.ctypes.data, -1
+        length = np.zeros(n, np.uint32)
+        status = np.zeros(n, np.int32)
+        rc = N.lib().srtp_fanout_host_ast(
+            self.h, src_seg.ctypes.data, src_seg.nbytes, src_off.ctypes.data, src_len.ctypes.data,
+            src_cap.ctypes.data, None if st_in is None else st_in.ctypes.data, m, src_idx.ctypes.data, tids_p,
+            tid0, seg.ctypes.data, seg.nbytes, off.ctypes.data, length.ctypes.data, cap.ctypes.data,
+            None if fl is None else fl.ctypes.data, None if rw is None else rw.ctypes.data, ast.ctypes.data,
+            status.ctypes.data, n)
+        N.check(rc, self.h, "srtp_fanout_host_ast")
         return length, status
 
     def fanout_stats(self) -> dict:
@@ -1306,11 +1385,61 @@ def fan_out_rw(pkts: Sequence[Optional[RawPacket]], transformers: Sequence[_SRTP
     return _fan_out(pkts, transformers, rewriters, exclusion)
 
 
+def abs_send_time(ns: int) -> int:
+    """AbsSendTimeEngine.setTimestamp's conversion (AbsSendTimeEngine.java:141-152) of a
+    time in nanoseconds, ``ns >= 0``, to the 24 bits of abs-send-time: 6.18 fixed-point
+    seconds, ``((ns // 1e9) % 64) << 18 | (ns % 1e9) * 2**18 // 1e9``."""
+    ns = int(ns)
+    if ns < 0:
+        raise ValueError("abs_send_time: ns >= 0")
+    b = 1000 * 1000 * 1000
+    return ((((ns // b) % 64) << 18) | ((ns % b) * (1 << 18) // b)) & 0x00FFFFFF
+
+
+def fan_out_ast(pkts: Sequence[Optional[RawPacket]], transformers: Sequence[_SRTPBase], rewriters, stampers,
+                exclusion=None):
+    """:func:`fan_out_rw` for streams that have abs-send-time negotiated.  In
+    the reference the last engine in front of a stream's SRTP transformer is
+    absSendTimeEngine (MediaStreamImpl.java:1018-1035), whose
+    replaceAbsSendTime (AbsSendTimeEngine.java:86-152) walks the copy's one-byte
+    header-extension elements and overwrites the three data bytes of the first
+    element that carries the stream's abs-send-time ID (if its len field is 2)
+    with the local send time.  ``stampers`` holds one stamper or None per
+    transformer.  A stamper is a callable ``g(pkt)``, called like a rewriter --
+    for every copy that would be written toward its transformer, after that
+    transformer's rewriter, in doWrite's order -- that returns None (this copy
+    is not stamped) or ``(ext_id, value)``: the stream's extension ID and the
+    24-bit time (:func:`abs_send_time`).  The walk and the stamp happen on the
+    GPU (srtp_fanout_host_ast), in the copy, before it is protected; a copy
+    without such an element leaves unchanged.  ``rewriters`` as in
+    :func:`fan_out_rw` (one or None per transformer).  Everything else is
+    :func:`fan_out`'s."""
+    transformers, rewriters, stampers = list(transformers), list(rewriters), list(stampers)
+    if len(rewriters) != len(transformers):
+        raise ValueError("fan_out_ast: one rewriter (or None) per transformer")
+    if len(stampers) != len(transformers):
+        raise ValueError("fan_out_ast: one stamper (or None) per transformer")
+    return _fan_out(pkts, transformers, rewriters, exclusion, stampers)
+
+
 _REWRITE_FIELDS = (("ssrc", N.REWRITE_SSRC, 0xFFFFFFFF), ("seq", N.REWRITE_SEQ, 0xFFFF),
                    ("timestamp", N.REWRITE_TIMESTAMP, 0xFFFFFFFF), ("pt", N.REWRITE_PT, 0x7F))
 
 
-def _fan_out(pkts, transformers, rewriters, exclusion):
+def _stamp_one(stamp, j, g, p):
+    """Entry j's abs-send-time record from stamper g (the engine behind the rewriter)."""
+    if g is None:
+        return
+    r = g(p)
+    if r is None:
+        return
+    ext_id, value = r
+    if not 0 <= int(ext_id) <= 255:
+        raise ValueError("fan_out_ast: a stamper returned the ID %r" % (ext_id,))
+    stamp["id"][j], stamp["value"][j], stamp["on"][j] = int(ext_id), int(value) & 0x00FFFFFF, 1
+
+
+def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None):
     pkts, transformers = list(pkts), list(transformers)
     out = [[None] * len(pkts) for _ in transformers]
     if not pkts or not transformers:
@@ -1333,13 +1462,21 @@ def _fan_out(pkts, transformers, rewriters, exclusion):
             if x is t or (t.packetPredicate is not None and pkts[i] is not None
                           and not t.packetPredicate(pkts[i])):
                 flags[i * T + k] |= N.PKT_FLAG_SKIP
-    rewrite = None
-    if rewriters is not None and any(f is not None for f in rewriters):
-        rewrite = np.zeros(len(pkts) * T, N.FANOUT_REWRITE_DTYPE)
+    rewrite = stamp = None
+    if stampers is not None and any(g is not None for g in stampers):
+        stamp = np.zeros(len(pkts) * T, N.FANOUT_AST_DTYPE)
+    if (rewriters is not None and any(f is not None for f in rewriters)) or stamp is not None:
+        if rewriters is not None and any(f is not None for f in rewriters):
+            rewrite = np.zeros(len(pkts) * T, N.FANOUT_REWRITE_DTYPE)
         for i, p in enumerate(pkts):  # doWrite's order
-            for k, f in enumerate(rewriters):
+            for k in range(T):
                 j = i * T + k
-                if f is None or p is None or flags[j] & N.PKT_FLAG_SKIP:
+                f = rewriters[k] if rewrite is not None else None
+                g = stampers[k] if stamp is not None else None
+                if p is None or flags[j] & N.PKT_FLAG_SKIP:
+                    continue
+                if f is None:
+                    _stamp_one(stamp, j, g, p)
                     continue
                 r = f(p)
                 if r is None:
@@ -1352,13 +1489,14 @@ def _fan_out(pkts, transformers, rewriters, exclusion):
                     if name in r:
                         rewrite[name][j] = int(r[name]) & lim
                         rewrite["mask"][j] |= bit
+                _stamp_one(stamp, j, g, p)
     step = (cap.astype(np.int64) + 15) & ~15
     off = np.concatenate(([0], np.cumsum(step)[:-1])).astype(np.int64)
     if int(off[-1] + step[-1]) >= 1 << 32:
         raise ValueError("fan_out: more than 4 GiB of copies")
     seg = np.zeros(int(off[-1] + step[-1]), np.uint8)
-    ln, st = eng.fanout_host_rw(tids, src_seg, src_off, src_len, src_cap, src_idx, seg, off.astype(np.uint32), cap,
-                                src_status, flags, rewrite)
+    ln, st = eng.fanout_host_ast(tids, src_seg, src_off, src_len, src_cap, src_idx, seg, off.astype(np.uint32), cap,
+                                 src_status, flags, rewrite, stamp)
     for j in np.nonzero(st == N.STATUS_OK)[0]:
         i, k = divmod(int(j), T)
         o = int(off[j])

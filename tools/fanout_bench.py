@@ -20,6 +20,19 @@
             route, 2^16 destinations at N in {1, 4, 16}: fanout_host_rw against
             what such a bridge does without it -- host expansion with the four
             setters applied (numpy, one thread, timed) plus transform_host.
+  --stamp   abs-send-time stamping (srtp_fanout_*_ast): 1200-byte sources with
+            X set and three one-byte-header elements, the abs-send-time one (ID
+            3) the second, no CSRC; every entry's record on, with a value of
+            its own per call.  Device route, n = 2^18, N = 8: fanout_device_ast
+            with stamp records only, and with rewrite records as well, against
+            fanout_device_rw and fanout_device over the same sources, the four
+            alternating call by call, HIP events.  Host route, 2^16
+            destinations at N in {1, 4, 16}: fanout_host_ast against host
+            expansion with the three bytes written into every copy (numpy,
+            timed) plus transform_host.  With --once: three fanout_device_ast
+            calls (stamp records only) and nothing else (a trace of
+            k_fanout_ast); --stamp-records off | miss takes the walk, or the
+            stamp, out of that trace.
   --plain   fanout_device of the --device shape and nothing else, 5 warm-up and
             20 timed calls (one side of a comparison between two builds of the
             library, a process each).
@@ -73,6 +86,14 @@ class Sources:
         self.len = np.full(m, LEN, np.uint32)
         self.cap = np.full(m, SRC_STRIDE, np.uint32)
         self.advance()
+
+    def with_extension(self):
+        """X set and a one-byte-header extension of three words: ID 1 (1 byte), the
+        abs-send-time element ID 3 (bytes 18..21, stamped at STAMP_AT), ID 5 (2 bytes)."""
+        self.rows[:, 0] = 0x90
+        self.rows[:, 12:28] = np.frombuffer(bytes([0xBE, 0xDE, 0, 3, 0x10, 0x77, 0x32, 0xA0, 0xA1, 0xA2, 0x51, 0x88, 0x99,
+                                                   0, 0, 0]), np.uint8)
+        return self
 
     def advance(self):
         self.seq = (self.base + np.arange(self.m) // self.ssrcs) & 0xFFFF  # this call's, host order
@@ -314,7 +335,7 @@ def device_setup(eng, n, fan):
     return w
 
 
-def timed_fanout(eng, w, rewrite):
+def timed_fanout(eng, w, rewrite, stamp=None):
     """One fan-out of fresh sources on the stream, between two HIP events: ms."""
     import torch
     w["src"].advance()
@@ -323,11 +344,18 @@ def timed_fanout(eng, w, rewrite):
     if rewrite is not None:
         rewrite.update()
         rw = torch.from_numpy(rewrite.rw.view(np.uint8)).cuda()
+    ast = None
+    if stamp is not None:
+        stamp.update()
+        ast = torch.from_numpy(stamp.ast.view(np.uint8)).cuda()
     torch.cuda.synchronize()
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     with torch.cuda.stream(w["stream"]):
         a.record()
-        if rw is None:
+        if ast is not None:
+            eng.fanout_device_ast(w["tids"], s_seg, w["s_off"], w["s_len"], w["s_cap"], w["idx"], w["seg"], w["off"],
+                                  w["ln"], w["cap"], w["st"], rw, ast, stream=w["stream"])
+        elif rw is None:
             eng.fanout_device(w["tids"], s_seg, w["s_off"], w["s_len"], w["s_cap"], w["idx"], w["seg"], w["off"],
                               w["ln"], w["cap"], w["st"], stream=w["stream"])
         else:
@@ -360,6 +388,100 @@ def rewrite_device_case(eng, n, fan):
             "record_bytes_read": 16 * n, "bytes_written": n * LEN}
 
 
+STAMP_AT = 19
+AST_DTYPE = np.dtype([("value", "<u4"), ("id", "u1"), ("on", "u1"), ("reserved", "<u2")])  # srtp_fanout_abs_send_time
+
+
+class Stamps:
+    """One record per destination entry, on, ID 3; update() gives every entry a new 24-bit value."""
+
+    def __init__(self, n, records="on"):
+        self.n, self.tick = n, 0
+        self.ast = np.zeros(n, AST_DTYPE)
+        # off: no entry walks; miss: every entry walks past all three elements and stamps nothing
+        self.ast["id"], self.ast["on"] = (9 if records == "miss" else 3), (0 if records == "off" else 1)
+        self.update()
+
+    def update(self):
+        self.tick += 1
+        self.ast["value"] = (np.arange(self.n, dtype=np.uint64) * 2654435761 + 977 * self.tick) & 0xFFFFFF
+
+    def bytes3(self):
+        v = self.ast["value"]
+        return np.stack([(v >> 16) & 0xFF, (v >> 8) & 0xFF, v & 0xFF], 1).astype(np.uint8)
+
+
+def stamp_device_case(eng, n, fan):
+    w = device_setup(eng, n, fan)
+    w["src"].with_extension()
+    tg, sp = Targets(w["src"], w["src_idx"], fan), Stamps(n)
+    t = {"fanout_device_ast_stamp_only": [], "fanout_device_ast_stamp_and_rewrite": [],
+         "fanout_device_rw_all_four_fields": [], "fanout_device": []}
+    pick = slice(None, None, max(1, n // 64))
+    for it in range(WARM + TIMED):
+        for name, (rw, st) in zip(t, ((None, sp), (tg, sp), (tg, None), (None, None))):
+            x = timed_fanout(eng, w, rw, st)
+            if st is not None:
+                got = w["seg"].view(n, DST_STRIDE)[pick, STAMP_AT:STAMP_AT + 3].cpu().numpy()
+                assert (got == sp.bytes3()[pick]).all()
+            if it >= WARM:
+                t[name].append(x)
+    res = {k: pct(v) for k, v in t.items()}
+    a, r, p = (res[k] for k in ("fanout_device_ast_stamp_only", "fanout_device_rw_all_four_fields", "fanout_device"))
+    spread = max(x["p90_ms"] - x["p10_ms"] for x in res.values())
+    res.update({"n": n, "N": fan, "m": w["m"], "ast_minus_rw_ms": a["median_ms"] - r["median_ms"],
+                "ast_minus_plain_ms": a["median_ms"] - p["median_ms"], "rw_minus_plain_ms": r["median_ms"] - p["median_ms"],
+                "widest_p90_minus_p10_ms": spread, "record_bytes_read": 8 * n, "bytes_written": n * LEN})
+    return res
+
+
+def stamp_host_case(eng, n, fan):
+    profile = "AES_CM_128_HMAC_SHA1_80"
+    m = n // fan
+    ts = peers(eng, profile, fan)
+    hs, hd = HostBuffer(m * SRC_STRIDE), HostBuffer(n * DST_STRIDE)
+    src = Sources(m, hs.array).with_extension()
+    src_idx = np.repeat(np.arange(m, dtype=np.int32), fan)
+    tids = np.tile(np.array([t.tid for t in ts], np.int32), m)
+    off = (np.arange(n, dtype=np.int64) * DST_STRIDE).astype(np.uint32)
+    cap = np.full(n, DST_CAP, np.uint32)
+    dst_rows = hd.array.reshape(n, DST_STRIDE)
+    sp = Stamps(n)
+    t_fan, t_old, t_expand = [], [], []
+    for it in range(WARM + TIMED):
+        src.advance()
+        sp.update()
+        t0 = time.perf_counter()
+        ln, st = eng.fanout_host_ast(tids, src.seg, src.off, src.len, src.cap, src_idx, hd.array, off, cap,
+                                     stamp=sp.ast)
+        t1 = time.perf_counter()
+        assert not st.any() and (ln == LEN + 10).all()
+        assert (dst_rows[:, STAMP_AT:STAMP_AT + 3] == sp.bytes3()).all()
+        src.advance()
+        sp.update()
+        t2 = time.perf_counter()
+        dst_rows[:, :LEN] = src.rows[src_idx]                # the N host-made copies
+        dst_rows[:, STAMP_AT:STAMP_AT + 3] = sp.bytes3()     # and the send chain's stamp on each (no walk: a known offset)
+        ln = np.full(n, LEN, np.uint32)
+        t3 = time.perf_counter()
+        st = eng.transform_host(False, tids, hd.array, off, ln, cap)
+        t4 = time.perf_counter()
+        assert not st.any()
+        if it >= WARM:
+            t_fan.append((t1 - t0) * 1e3)
+            t_old.append((t4 - t2) * 1e3)
+            t_expand.append((t3 - t2) * 1e3)
+    for t in ts:
+        t.close()
+    hs.close()
+    hd.close()
+    a, b = pct(t_fan), pct(t_old)
+    return {"profile": profile, "N": fan, "n": n, "m": m, "fanout_host_ast": a,
+            "expand_stamp_plus_transform_host": b, "host_expansion_and_stamp_alone": pct(t_expand),
+            "h2d_bytes_fanout_ast": m * SRC_STRIDE + 3 * 4 * m + 4 * 4 * n + 8 * n,  # ... and the records
+            "h2d_bytes_expand": n * DST_STRIDE + 4 * 4 * n, "verdict": verdict(a, b)}
+
+
 def plain_device_case(eng, n, fan):
     w = device_setup(eng, n, fan)
     t = [timed_fanout(eng, w, None) for _ in range(WARM + TIMED)][WARM:]
@@ -373,11 +495,14 @@ def main():
     ap.add_argument("--once", action="store_true")
     ap.add_argument("--rewrite", action="store_true")
     ap.add_argument("--plain", action="store_true")
+    ap.add_argument("--stamp", action="store_true")
+    ap.add_argument("--stamp-records", choices=("on", "off", "miss"), default="on",
+                    help="with --once --stamp: every record on (default), off, or on under the ID of no element")
     ap.add_argument("--log2n-host", type=int, default=16)
     ap.add_argument("--log2n-device", type=int, default=18)
     ap.add_argument("--out")
     args = ap.parse_args()
-    if args.device or args.once or args.rewrite or args.plain:
+    if args.device or args.once or args.rewrite or args.plain or args.stamp:
         import torch  # asked before the engine library initialises HIP: torch caches its first answer
         assert torch.cuda.is_available()
     eng = SRTPEngine(device=0, max_contexts=1 << 19, max_factories=256, max_transformers=256,
@@ -387,7 +512,15 @@ def main():
     if args.host:
         res["host"] = [host_case(eng, prof, 1 << args.log2n_host, fan)
                        for prof in ("AES_CM_128_HMAC_SHA1_80", "AEAD_AES_128_GCM") for fan in (1, 2, 4, 8, 16)]
-    if args.once and args.rewrite:  # three fanout_device_rw calls and nothing else (a trace of k_fanout_rw)
+    if args.once and args.stamp:  # three fanout_device_ast calls and nothing else (a trace of k_fanout_ast)
+        w = device_setup(eng, 1 << args.log2n_device, 8)
+        w["src"].with_extension()
+        sp = Stamps(1 << args.log2n_device, args.stamp_records)
+        res["device"] = {"once_ast_ms": [timed_fanout(eng, w, None, sp) for _ in range(3)]}
+    elif args.stamp:
+        res["stamp_device"] = stamp_device_case(eng, 1 << args.log2n_device, 8)
+        res["stamp_host"] = [stamp_host_case(eng, 1 << args.log2n_host, fan) for fan in (1, 4, 16)]
+    elif args.once and args.rewrite:  # three fanout_device_rw calls and nothing else (a trace of k_fanout_rw)
         w = device_setup(eng, 1 << args.log2n_device, 8)
         tg = Targets(w["src"], w["src_idx"], 8)
         res["device"] = {"once_rw_ms": [timed_fanout(eng, w, tg) for _ in range(3)]}
