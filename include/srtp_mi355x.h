@@ -64,7 +64,7 @@
 extern "C" {
 #endif
 
-#define SRTP_MI355X_ABI_VERSION 4
+#define SRTP_MI355X_ABI_VERSION 5
 
 /* SRTPPolicy constants (transform/srtp/SRTPPolicy.java:29-63) */
 #define SRTP_NULL_ENCRYPTION 0
@@ -299,8 +299,9 @@ int srtp_fanout_job(int32_t src_idx, int32_t m, int32_t src_len, int32_t src_cap
  * on the device route, where the records are not read back, they are ignored.
  * `reserved` is ignored.  The rule knows nothing of the transformer's kind: for
  * an SRTCP transformer only mask 0 makes sense, which is the caller's
- * responsibility.  Payload rewriting (RTX, RED, FEC) and RTCP rewriting are not
- * done here: such a packet goes to its peer as a host-made copy. */
+ * responsibility.  The RTX OSN and the FEC SN base are srtp_fanout_device_pay's
+ * (below); RTCP rewriting is not done here: such a packet goes to its peer as
+ * a host-made copy. */
 typedef struct { uint32_t mask, ssrc, timestamp; uint16_t seq; uint8_t pt, reserved; } srtp_fanout_rewrite;
 #define SRTP_REWRITE_SSRC 0x1u       /* RawPacket.setSSRC:           bytes 8..11 = ssrc, big-endian */
 #define SRTP_REWRITE_SEQ 0x2u        /* RawPacket.setSequenceNumber: bytes 2..3  = seq, big-endian */
@@ -391,6 +392,71 @@ int srtp_fanout_host_ast(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
 int srtp_fanout_ast_job(const uint8_t *pkt, uint32_t bound, int32_t src_idx, int32_t m, int32_t src_len,
                         int32_t src_cap, int32_t src_status, int32_t dst_cap, uint32_t flags,
                         const srtp_fanout_abs_send_time *stamp, int32_t *out);
+
+/* Fan-out that patches the payload per destination: the last per-peer bytes of
+ * ExtendedSequenceNumberInterval.rewriteRTP (ExtendedSequenceNumberInterval.java:
+ * 163-229), which the rewriting engine writes before SRTP sees the packet.
+ *   RTX  rewriteRTX (:261-284): pkt.setOriginalSequenceNumber((short) sn) is
+ *        writeShort(getHeaderLength(), sn) (RawPacket.java:1018-1022,
+ *        1334-1337): two bytes, big-endian, at the start of the payload -- the
+ *        peer's rewritten number of the original packet.
+ *   FEC  rewriteFEC (:346-386), plain or as the matching block of a RED packet
+ *        (rewriteRED, :307-333): the SN base of the FEC header, buf[off + 2]
+ *        and buf[off + 3].
+ * The payload is ciphered (under AES-GCM sealed), so the bytes are written into
+ * entry j's copy before the protect chain runs.  The host keeps everything
+ * that chooses values -- the rewriter's intervals, rtx2primary / ssrc2fec /
+ * ssrc2red, the RED block walk, getHeaderLength() of the source -- and hands
+ * the device one 8-byte record per destination entry with two patches: b0[0],
+ * b0[1] go to packet bytes at0, at0 + 1, then b1[0], b1[1] to at1, at1 + 1.
+ * An all-zero record does nothing.
+ *
+ * With c = min(src_len, src_cap, cap[j]): a patch is on exactly when the entry
+ * is not skipped, at >= 12 and c > at.  A patch below byte 12 is refused whole
+ * (those bytes are the setters').  Of a patch that is on, byte i of {at, at + 1}
+ * is written iff i < c, as the reference's two writeByte calls: at == c - 1
+ * writes the first byte only.  No byte is written that the copy did not write;
+ * the source segment is never written.  Order within an entry: patch 0, patch 1
+ * (where they overlap patch 1 wins), then the abs-send-time stamp (where they
+ * overlap the stamp wins; its walk reads the patched bytes) -- the reference's
+ * chain, ssrcRewritingEngine (MediaStreamImpl.java:998) in front of
+ * absSendTimeEngine (:1018-1020).  The rewrite records touch bytes 1..11 only
+ * and apply in either order.  The record carries bytes and has no opinion on
+ * what they mean. */
+typedef struct srtp_fanout_payload {
+    uint16_t at0; uint8_t b0[2];   /* patch 0: b0[0], b0[1] go to packet bytes at0, at0 + 1; at0 == 0: off */
+    uint16_t at1; uint8_t b1[2];   /* patch 1, likewise, applied after patch 0 */
+} srtp_fanout_payload;
+/* srtp_fanout_device_ast / srtp_fanout_host_ast with one more argument after
+ * stamp: pay, n records (k_fanout_pay).  pay == NULL is the _ast call, exactly.
+ * With pay set, rewrite and stamp may each be NULL.  Device route: a device
+ * array, 8-byte aligned (else SRTP_EINVAL before any launch).  Host route: a
+ * host array, staged like src_idx, rewrite and stamp.  Replaces, per copy,
+ * rewriteRTX's setOriginalSequenceNumber (ExtendedSequenceNumberInterval.java:
+ * 261-284) and rewriteFEC's two stores (:346-386). */
+int srtp_fanout_device_pay(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
+                           const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status,
+                           uint32_t m, const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                           const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                           const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
+                           const srtp_fanout_payload *pay, int32_t *status, uint32_t n, void *stream);
+int srtp_fanout_host_pay(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_bytes, const uint32_t *src_off,
+                         const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status,
+                         uint32_t m, const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                         size_t seg_bytes, const uint32_t *off, uint32_t *len, const uint32_t *cap,
+                         const uint32_t *flags, const srtp_fanout_rewrite *rewrite,
+                         const srtp_fanout_abs_send_time *stamp, const srtp_fanout_payload *pay,
+                         int32_t *status, uint32_t n);
+/* The patch rule of one destination entry (host only; fanout_job.h, the text
+ * k_fanout_pay compiles) over the caller's piece: the first seven arguments are
+ * srtp_fanout_job's; words_in are the four little-endian 32-bit words of bytes
+ * 16 q .. 16 q + 15 of the copy (q >= 0).  words_out = the piece with patch 0,
+ * then patch 1 applied: what RawPacket.writeShort (RawPacket.java:1334-1337)
+ * and rewriteFEC's stores (ExtendedSequenceNumberInterval.java:383-384) leave of
+ * it, under the rules above. */
+int srtp_fanout_pay_job(int32_t src_idx, int32_t m, int32_t src_len, int32_t src_cap, int32_t src_status,
+                        int32_t dst_cap, uint32_t flags, const srtp_fanout_payload *pay, int32_t q,
+                        const uint32_t *words_in, uint32_t *words_out);
 
 /* The engine's own non-blocking stream, created with the engine so that each
  * engine gets a hardware queue of its own (streams created later may share

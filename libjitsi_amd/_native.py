@@ -40,7 +40,7 @@ DEBUG_NO_GCM_SPEC = 0x80     # GCM unprotect always in two passes (tag check, wa
 DEBUG_FORCE_GCM_SPEC = 0x100  # ... always in one (k_gcm<open> / <fix>), on the multi-kernel path
 GCM_FIX_NONE, GCM_FIX_RESTORE, GCM_FIX_DECIPHER = 0, 1, 2  # srtp_gcm_fix_action (bits)
 GCM_BATCH_WAVE = 0x1         # srtp_aes_gcm_device_ex: a wave per packet
-ABI_VERSION = 4
+ABI_VERSION = 5
 AGG_SEAL_IDLE = 0x1
 PKT_FLAG_DISCARD, PKT_FLAG_SILENCE, PKT_FLAG_SKIP = 0x2, 0x4, 0x80000000
 RC = {0: "SRTP_OK", -1: "SRTP_EINVAL", -2: "SRTP_ENOMEM", -3: "SRTP_EFULL", -4: "SRTP_EDEVICE",
@@ -93,6 +93,7 @@ EXPORTED = [
     "srtp_fanout_device", "srtp_fanout_host", "srtp_engine_fanout_stats", "srtp_fanout_job",
     "srtp_fanout_device_rw", "srtp_fanout_host_rw", "srtp_fanout_rewrite_job",
     "srtp_fanout_device_ast", "srtp_fanout_host_ast", "srtp_fanout_ast_job",
+    "srtp_fanout_device_pay", "srtp_fanout_host_pay", "srtp_fanout_pay_job",
 ]
 STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 
@@ -218,6 +219,15 @@ class FanoutAbsSendTime(C.Structure):
 
 # numpy's view of an array of srtp_fanout_abs_send_time (fanout_host_ast)
 FANOUT_AST_DTYPE = np.dtype([("value", "<u4"), ("id", "u1"), ("on", "u1"), ("reserved", "<u2")])
+
+
+class FanoutPayload(C.Structure):
+    """srtp_fanout_payload (include/srtp_mi355x.h): one destination entry's two payload patches"""
+    _fields_ = [("at0", C.c_uint16), ("b0", C.c_uint8 * 2), ("at1", C.c_uint16), ("b1", C.c_uint8 * 2)]
+
+
+# numpy's view of an array of srtp_fanout_payload (fanout_host_pay)
+FANOUT_PAYLOAD_DTYPE = np.dtype([("at0", "<u2"), ("b0", "u1", (2,)), ("at1", "<u2"), ("b1", "u1", (2,))])
 
 DTLS_AEAD = 0x1
 GCM_HDR_THROW = -0x80000000
@@ -373,6 +383,12 @@ def lib() -> C.CDLL:
                                        vp, vp, vp, vp, vp, u32]
     L.srtp_fanout_ast_job.argtypes = [vp, u32, i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutAbsSendTime),
                                       C.POINTER(C.c_int32)]
+    L.srtp_fanout_device_pay.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                         vp, u32, vp]
+    L.srtp_fanout_host_pay.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, u32, vp, vp, i32, vp, C.c_size_t, vp, vp,
+                                       vp, vp, vp, vp, vp, vp, u32]
+    L.srtp_fanout_pay_job.argtypes = [i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutPayload), i32,
+                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.srtp_engine_fanout_stats.argtypes = [vp, C.POINTER(FanoutStats)]
     L.srtp_fanout_job.argtypes = [i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutPlan)]
     L.srtp_trailer_room.argtypes = [i32]

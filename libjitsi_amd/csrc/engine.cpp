@@ -115,9 +115,10 @@ struct srtp_engine {
     unsigned long long *d_fan_skipped = nullptr;
     uint8_t *hs_seg = nullptr;
     size_t hs_seg_bytes = 0;
-    uint32_t hs_m = 0, hs_n = 0, hs_rw_n = 0, hs_ast_n = 0;
+    uint32_t hs_m = 0, hs_n = 0, hs_rw_n = 0, hs_ast_n = 0, hs_pay_n = 0;
     srtp_fanout_rewrite *hs_rw = nullptr; // srtp_fanout_host_rw's records, staged like hs_idx
     srtp_fanout_abs_send_time *hs_ast = nullptr; // srtp_fanout_host_ast's records, likewise
+    srtp_fanout_payload *hs_pay = nullptr; // srtp_fanout_host_pay's records, likewise
     uint32_t *hs_off = nullptr, *hs_len = nullptr, *hs_cap = nullptr;
     int32_t *hs_status = nullptr, *hs_idx = nullptr;
     uint64_t fan_calls = 0, fan_sources = 0, fan_destinations = 0, fan_src_bytes = 0;
@@ -616,7 +617,7 @@ void srtp_engine_destroy(srtp_engine *e) {
     void *ptrs[] = {e->d_keysets, e->d_extkeys, e->d_tfkeys, e->d_skkeys, e->d_gcmkeys, e->d_gcmpow, e->d_factories, e->d_transformers, e->d_ctx_keys, e->d_ctx,
                     e->d_far, e->e_min, e->ctl, e->d_count, e->d_counters, e->h_seg, e->h_off, e->h_len,
                     e->h_cap, e->h_flags, e->h_status, e->h_tids, e->fan_flags, e->d_fan_skipped, e->hs_seg,
-                    e->hs_off, e->hs_len, e->hs_cap, e->hs_status, e->hs_idx, e->hs_rw, e->hs_ast};
+                    e->hs_off, e->hs_len, e->hs_cap, e->hs_status, e->hs_idx, e->hs_rw, e->hs_ast, e->hs_pay};
     for (void *p : ptrs) dfree(p);
     if (e->ev_last) (void)hipEventDestroy(e->ev_last);
     if (e->ev_dev) (void)hipEventDestroy(e->ev_dev);
@@ -1076,12 +1077,15 @@ static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t 
                          const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
                          const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
                          const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
-                         int32_t *status, uint32_t n, hipStream_t s, bool dev_event) {
+                         const srtp_fanout_payload *pay, int32_t *status, uint32_t n, hipStream_t s,
+                         bool dev_event) {
     int rc = check_fanout(e, {src_seg, src_off, src_len, src_cap, src_idx, seg, off, len, cap, status}, m, n);
     if (rc == SRTP_OK && ((uintptr_t)rewrite & 15u)) // k_fanout_rw loads a record in one 16-byte piece
         rc = fail(e, SRTP_EINVAL, "rewrite must be 16-byte aligned");
     if (rc == SRTP_OK && ((uintptr_t)stamp & 7u)) // k_fanout_ast loads a record in one 8-byte piece
         rc = fail(e, SRTP_EINVAL, "stamp must be 8-byte aligned");
+    if (rc == SRTP_OK && ((uintptr_t)pay & 7u)) // k_fanout_pay loads a record in one 8-byte piece
+        rc = fail(e, SRTP_EINVAL, "pay must be 8-byte aligned");
     if (rc == SRTP_OK) rc = check_tid(e, tids != nullptr, tid);
     if (rc == SRTP_OK) rc = ensure_scratch(e, n);
     if (rc != SRTP_OK) return rc;
@@ -1105,7 +1109,7 @@ static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t 
     f.flags_out = e->fan_flags;
     f.skipped = e->d_fan_skipped;
     f.n = n;
-    HIPCHK(e, launch_fanout(f, s, rewrite, stamp));
+    HIPCHK(e, launch_fanout(f, s, rewrite, stamp, pay));
     rc = transform_locked(e, 0, tids, tid, seg, off, len, cap, e->fan_flags, status, n, s, -1, dev_event);
     if (rc != SRTP_OK) return rc;
     e->fan_calls++;
@@ -1114,18 +1118,28 @@ static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t 
     return SRTP_OK;
 }
 
+int srtp_fanout_device_pay(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
+                           const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status, uint32_t m,
+                           const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                           const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                           const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
+                           const srtp_fanout_payload *pay, int32_t *status, uint32_t n, void *stream) {
+    if (!e) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (n == 0) return SRTP_OK;
+    GUARD(e);
+    return fanout_locked(e, src_seg, src_off, src_len, src_cap, src_status, m, src_idx, tids, tid, seg, off, len,
+                         cap, flags, rewrite, stamp, pay, status, n, (hipStream_t)stream, true);
+}
+
 int srtp_fanout_device_ast(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
                            const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status, uint32_t m,
                            const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
                            const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
                            const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
                            int32_t *status, uint32_t n, void *stream) {
-    if (!e) return SRTP_EINVAL;
-    std::lock_guard<std::mutex> g(e->mu);
-    if (n == 0) return SRTP_OK;
-    GUARD(e);
-    return fanout_locked(e, src_seg, src_off, src_len, src_cap, src_status, m, src_idx, tids, tid, seg, off, len,
-                         cap, flags, rewrite, stamp, status, n, (hipStream_t)stream, true);
+    return srtp_fanout_device_pay(e, src_seg, src_off, src_len, src_cap, src_status, m, src_idx, tids, tid, seg, off,
+                                  len, cap, flags, rewrite, stamp, nullptr, status, n, stream);
 }
 
 int srtp_fanout_device_rw(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
@@ -1169,6 +1183,16 @@ int srtp_fanout_host_ast(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
                          const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
                          const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
                          int32_t *status, uint32_t n) {
+    return srtp_fanout_host_pay(e, src_seg, src_seg_bytes, src_off, src_len, src_cap, src_status, m, src_idx, tids,
+                                tid, seg, seg_bytes, off, len, cap, flags, rewrite, stamp, nullptr, status, n);
+}
+
+int srtp_fanout_host_pay(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_bytes, const uint32_t *src_off,
+                         const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status, uint32_t m,
+                         const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg, size_t seg_bytes,
+                         const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                         const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
+                         const srtp_fanout_payload *pay, int32_t *status, uint32_t n) {
     if (!e) return SRTP_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     if (n == 0) return SRTP_OK;
@@ -1188,7 +1212,7 @@ int srtp_fanout_host_ast(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
     if (rc != SRTP_OK) return rc;
     const size_t need = (src_seg_bytes + 15) & ~(size_t)15;
     if ((need > e->hs_seg_bytes || m > e->hs_m || n > e->hs_n || (rewrite && n > e->hs_rw_n) ||
-         (stamp && n > e->hs_ast_n)) &&
+         (stamp && n > e->hs_ast_n) || (pay && n > e->hs_pay_n)) &&
         e->have_last) {
         rc = quiesce(e); // the source staging may still be read by an enqueued fan-out
         if (rc != SRTP_OK) return rc;
@@ -1198,6 +1222,7 @@ int srtp_fanout_host_ast(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
     if (rc == SRTP_OK) rc = grow_staging(e, &e->hs_n, n, &e->hs_idx);
     if (rc == SRTP_OK && rewrite) rc = grow_staging(e, &e->hs_rw_n, n, &e->hs_rw);
     if (rc == SRTP_OK && stamp) rc = grow_staging(e, &e->hs_ast_n, n, &e->hs_ast);
+    if (rc == SRTP_OK && pay) rc = grow_staging(e, &e->hs_pay_n, n, &e->hs_pay);
     if (rc != SRTP_OK) return rc;
     // only the source segment and the small arrays cross to the device
     HIPCHK(e, hipMemcpyAsync(e->hs_seg, src_seg, src_seg_bytes, hipMemcpyHostToDevice, s));
@@ -1208,6 +1233,7 @@ int srtp_fanout_host_ast(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
     HIPCHK(e, hipMemcpyAsync(e->hs_idx, src_idx, n * 4ull, hipMemcpyHostToDevice, s));
     if (rewrite) HIPCHK(e, hipMemcpyAsync(e->hs_rw, rewrite, n * sizeof *rewrite, hipMemcpyHostToDevice, s));
     if (stamp) HIPCHK(e, hipMemcpyAsync(e->hs_ast, stamp, n * sizeof *stamp, hipMemcpyHostToDevice, s));
+    if (pay) HIPCHK(e, hipMemcpyAsync(e->hs_pay, pay, n * sizeof *pay, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(e->h_off, off, n * 4ull, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(e->h_cap, cap, n * 4ull, hipMemcpyHostToDevice, s));
     if (flags) HIPCHK(e, hipMemcpyAsync(e->h_flags, flags, n * 4ull, hipMemcpyHostToDevice, s));
@@ -1215,7 +1241,7 @@ int srtp_fanout_host_ast(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
     rc = fanout_locked(e, e->hs_seg, e->hs_off, e->hs_len, e->hs_cap, src_status ? e->hs_status : nullptr, m,
                        e->hs_idx, tids ? e->h_tids : nullptr, tid, e->h_seg, e->h_off, e->h_len, e->h_cap,
                        flags ? e->h_flags : nullptr, rewrite ? e->hs_rw : nullptr, stamp ? e->hs_ast : nullptr,
-                       e->h_status, n, s, false);
+                       pay ? e->hs_pay : nullptr, e->h_status, n, s, false);
     if (rc != SRTP_OK) return rc;
     e->fan_src_bytes += src_seg_bytes;
     HIPCHK(e, hipMemcpyAsync(seg, e->h_seg, seg_bytes, hipMemcpyDeviceToHost, s));
@@ -1296,6 +1322,26 @@ int srtp_fanout_ast_job(const uint8_t *pkt, uint32_t bound, int32_t src_idx, int
     const FanoutJob j = fanout_job(src_idx, m, src_len, src_cap, src_status, dst_cap, flags);
     const HostBytes rd{pkt, bound > 65535u ? 65535 : (int)bound};
     *out = fanout_ast_find(rd, j, src_len, src_cap, dst_cap, stamp->on, stamp->id);
+    return SRTP_OK;
+}
+
+int srtp_fanout_pay_job(int32_t src_idx, int32_t m, int32_t src_len, int32_t src_cap, int32_t src_status,
+                        int32_t dst_cap, uint32_t flags, const srtp_fanout_payload *pay, int32_t q,
+                        const uint32_t *words_in, uint32_t *words_out) {
+    if (!pay || q < 0 || !words_in || !words_out) return SRTP_EINVAL;
+    static_assert(sizeof(srtp_fanout_payload) == 8 && offsetof(srtp_fanout_payload, b0) == 2 &&
+                      offsetof(srtp_fanout_payload, at1) == 4 && offsetof(srtp_fanout_payload, b1) == 6 &&
+                      alignof(srtp_fanout_payload) <= 8,
+                  "k_fanout_pay loads a record as two 32-bit words");
+    const FanoutJob j = fanout_job(src_idx, m, src_len, src_cap, src_status, dst_cap, flags);
+    const int c = fanout_pay_bound(j, src_len, src_cap, dst_cap);
+    FanoutPiece p{words_in[0], words_in[1], words_in[2], words_in[3]};
+    p = fanout_pay_piece(p, q, pay->at0, pay->b0[0], pay->b0[1], c);
+    p = fanout_pay_piece(p, q, pay->at1, pay->b1[0], pay->b1[1], c);
+    words_out[0] = p.w0;
+    words_out[1] = p.w1;
+    words_out[2] = p.w2;
+    words_out[3] = p.w3;
     return SRTP_OK;
 }
 

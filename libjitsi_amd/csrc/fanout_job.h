@@ -88,6 +88,44 @@
 // The four setters touch bytes 1..11 and the walk reads b[0] of the fixed header
 // only, which no setter writes; the stamp lies at byte 17 or later.  So the two
 // rules are independent of the order they are applied in.
+//
+// Payload patches (srtp_fanout_device_pay / _host_pay): entry j may also carry
+// an 8-byte record of two patches (at0, b0[2], at1, b1[2]), the last things
+// ExtendedSequenceNumberInterval.rewriteRTP writes with a value of the peer's:
+//   RTX  rewriteRTX (:261-284): setOriginalSequenceNumber = writeShort(
+//        getHeaderLength(), sn) (RawPacket.java:1018-1022, 1334-1337), two
+//        bytes, big-endian, at the start of the payload
+//   FEC  rewriteFEC (:346-386), plain or as a RED packet's block (rewriteRED,
+//        :307-333): the SN base of the FEC header, buf[off + 2], buf[off + 3]
+// Which offset and which bytes is the host's business (getHeaderLength, the RED
+// block walk, the peer's numbers): the rule gets offsets and bytes and knows no
+// protocol.  Plain functions again, compiled alike by the host
+// (srtp_fanout_pay_job, tools/fanout_pay_check.cpp) and by k_fanout_pay:
+//   fanout_pay_bound   c = min(src_len, src_cap, dst_cap), clamped as above,
+//             when the entry is not skipped and copy_bytes >= c; else 0.
+//   fanout_pay_on      a patch is on exactly when at >= 12 and c > at.  A patch
+//             below byte 12 is refused whole (at = 0 is the record's "off"):
+//             those bytes are the setters', so patches and setters are disjoint
+//             and apply in either order.
+//   which bytes        byte i of {at, at + 1} of a patch that is on is written
+//             iff i < c -- per byte, as the reference's two writeByte calls:
+//             with at == c - 1 the first byte is written and the second is
+//             not.  No byte is written that the copy did not write.
+//   fanout_pay_piece   the 16-byte piece q of the copy (four little-endian
+//             words) with whichever of those bytes lie in it replaced by v0
+//             (at) and v1 (at + 1), every other byte untouched: a patch that
+//             straddles two pieces is two calls.  Selects only, no branch.
+//   the order          patch 0, then patch 1 (where they overlap patch 1 wins),
+//             then the abs-send-time stamp (where they overlap the stamp wins):
+//             the reference's chain, ssrcRewritingEngine (MediaStreamImpl.java:
+//             998) in front of absSendTimeEngine (:1018-1020).  The stamp can
+//             reach payload bytes through its kept quirk: a match in the four
+//             bytes past the extension is stamped into the first payload bytes,
+//             where the OSN lies.  The reference's walk reads the copy the
+//             rewriting engine has already written, and the same quirk lets it
+//             read the first payload bytes as an element: so the walk reads
+//             every byte through fanout_pay_byte (the byte as both patches
+//             leave it), not the source's.
 #pragma once
 #include <stdint.h>
 
@@ -259,6 +297,54 @@ SRTP_FANOUT_HD inline FanoutPiece fanout_ast_piece(const FanoutPiece &piece, int
     o.w2 = fanout_ast_word(piece.w2, s - 8, v);
     o.w3 = fanout_ast_word(piece.w3, s - 12, v);
     return o;
+}
+
+// ---- payload patches (srtp_fanout_device_pay / _host_pay, k_fanout_pay)
+
+// c = min(src_len, src_cap, dst_cap) clamped as above when entry j can be patched at all -- it is
+// not skipped and every byte below c is one the copy writes -- else 0.
+SRTP_FANOUT_HD inline int fanout_pay_bound(const FanoutJob &j, int src_len, int src_cap, int dst_cap) {
+    if (j.flags_out & kFanFlagSkip) return 0;
+    if (src_len < 0 || src_cap < 0 || dst_cap < 0) return 0;
+    int c = fanout_clamp(src_len);
+    const int sc = fanout_clamp(src_cap), dc = fanout_clamp(dst_cap);
+    if (c > sc) c = sc;
+    if (c > dc) c = dc;
+    return j.copy_bytes >= c ? c : 0;
+}
+
+// A patch at `at` (0 .. 65535, the record's uint16) of an entry whose bound is c.
+SRTP_FANOUT_HD inline bool fanout_pay_on(int at, int c) { return at >= kFanHeaderBytes && c > at; }
+
+// One word of a piece: `s` is where the patch starts relative to the word's first byte; w0 / w1:
+// whether the patch's first / second byte is written at all.  Selects only, as fanout_ast_word.
+SRTP_FANOUT_HD inline uint32_t fanout_pay_word(uint32_t w, int s, uint32_t v0, uint32_t v1, bool w0, bool w1) {
+    const bool in0 = w0 && s >= 0 && s <= 3, in1 = w1 && s >= -1 && s <= 2;
+    const int up0 = in0 ? 8 * s : 0, up1 = in1 ? 8 * (s + 1) : 0; // 0 .. 24
+    const uint32_t m = (in0 ? 0xFFu << up0 : 0u) | (in1 ? 0xFFu << up1 : 0u);
+    const uint32_t x = (in0 ? (v0 & 0xFFu) << up0 : 0u) | (in1 ? (v1 & 0xFFu) << up1 : 0u);
+    return (w & ~m) | x;
+}
+
+// Piece q with whichever of the bytes at (v0), at + 1 (v1) are written and lie in it replaced:
+// nothing when the patch is off, the first byte only when at == c - 1.
+SRTP_FANOUT_HD inline FanoutPiece fanout_pay_piece(const FanoutPiece &piece, int q, int at, uint32_t v0, uint32_t v1,
+                                                   int c) {
+    const bool w0 = fanout_pay_on(at, c), w1 = w0 && at + 1 < c;
+    const int s = at - 16 * q;
+    FanoutPiece o;
+    o.w0 = fanout_pay_word(piece.w0, s, v0, v1, w0, w1);
+    o.w1 = fanout_pay_word(piece.w1, s - 4, v0, v1, w0, w1);
+    o.w2 = fanout_pay_word(piece.w2, s - 8, v0, v1, w0, w1);
+    o.w3 = fanout_pay_word(piece.w3, s - 12, v0, v1, w0, w1);
+    return o;
+}
+
+// Byte i of the copy (b as the source holds it) behind one patch: what fanout_pay_piece leaves
+// there.  The abs-send-time walk of a patched entry reads through this, patch 0 then patch 1.
+SRTP_FANOUT_HD inline int fanout_pay_byte(int b, int i, int at, uint32_t v0, uint32_t v1, int c) {
+    const bool w0 = fanout_pay_on(at, c), w1 = w0 && at + 1 < c;
+    return w0 && i == at ? (int)(v0 & 0xFFu) : w1 && i == at + 1 ? (int)(v1 & 0xFFu) : b;
 }
 
 } // namespace srtp

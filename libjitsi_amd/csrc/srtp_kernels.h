@@ -181,9 +181,13 @@ struct FanoutArgs {
 // fanout_rewrite_applies says so (k_fanout_rw).  stamp: null, or n 8-byte
 // records (srtp_fanout_abs_send_time), 8-byte aligned, in device memory: entry
 // j's copy gets stamp[j]'s three bytes where fanout_ast_find finds the element
-// (k_fanout_ast, with or without rewrite; the only instance that uses LDS)
+// (k_fanout_ast, with or without rewrite).  pay: null, or n 8-byte records
+// (srtp_fanout_payload), 8-byte aligned, in device memory: entry j's copy gets
+// pay[j]'s two patches where fanout_pay_on says so (k_fanout_pay, with or
+// without rewrite and stamp; picked only when pay is not null).  The two last
+// instances are the ones that use LDS.
 hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s, const void *rewrite = nullptr,
-                         const void *stamp = nullptr);
+                         const void *stamp = nullptr, const void *pay = nullptr);
 // unprotect: statuses/lengths out; undo/redo the rare speculation misses (after the walk)
 hipError_t launch_unprotect_fix(const BundleArgs &a, hipStream_t s);
 // AES-F8 packets after the final statuses: protect (F8 + HMAC + trailer) or

@@ -7315,10 +7315,162 @@ __global__ __launch_bounds__(kGatherBlock) void k_fanout_ast(FanoutArgs f, const
     }
 }
 
-hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s, const void *rewrite, const void *stamp) {
+// The payload-patching instance (k_fanout_pay, srtp_fanout_*_pay): entry j
+// carries the record pay[j] (at0 | b0 << 16, at1 | b1 << 16: two patches of two
+// bytes each, fanout_job.h) and, where given, rewrite[j] and stamp[j] as above.
+// In front of the copy loop fanout_pay_bound gives each entry's c from its own
+// job, and fanout_pay_on says from its own record which of its two patches are
+// on; an entry without bytes, which borrows its partner's pointers, has c = 0
+// and no patch, and the partner's record goes with the partner's stores only.
+// The copy loop is k_fanout_ast's with every stored piece passed through
+// fanout_pay_piece where its index is at >> 4 or (at + 1) >> 4 -- patch 0, then
+// patch 1 -- between fan_patched and fan_stamped: the reference's order,
+// ssrcRewritingEngine in front of absSendTimeEngine.  With stamp null no row
+// is staged, no walk runs and no walk_sync is reached (the same for every
+// lane); with it the walk reads each byte as the patches leave it
+// (fanout_pay_byte), as the reference's reads the rewritten copy.
+struct FanPay {
+    int c;            // fanout_pay_bound; 0: no patch
+    int at0, at1;     // the record's offsets
+    uint32_t v00, v01, v10, v11;
+    bool on0, on1;
+};
+// rec: the entry's own record as loaded; c: its own bound
+__device__ __forceinline__ FanPay fan_pay(const uint2 &rec, int c) {
+    FanPay p;
+    p.c = c;
+    p.at0 = (int)(rec.x & 0xFFFFu);
+    p.at1 = (int)(rec.y & 0xFFFFu);
+    p.v00 = (rec.x >> 16) & 0xFFu;
+    p.v01 = rec.x >> 24;
+    p.v10 = (rec.y >> 16) & 0xFFu;
+    p.v11 = rec.y >> 24;
+    p.on0 = fanout_pay_on(p.at0, c);
+    p.on1 = fanout_pay_on(p.at1, c);
+    return p;
+}
+__device__ __forceinline__ uint4 fan_paid_one(const uint4 &piece, uint32_t q, bool on, int at, uint32_t v0,
+                                              uint32_t v1, int c) {
+    const bool hit = on && ((int)q == (at >> 4) || (int)q == ((at + 1) >> 4));
+    const FanoutPiece p = fanout_pay_piece(FanoutPiece{piece.x, piece.y, piece.z, piece.w}, (int)q, at, v0, v1, c);
+    uint4 out;
+    out.x = hit ? p.w0 : piece.x;
+    out.y = hit ? p.w1 : piece.y;
+    out.z = hit ? p.w2 : piece.z;
+    out.w = hit ? p.w3 : piece.w;
+    return out;
+}
+// Piece q as it is stored: patch 0, then patch 1, each where it holds one of the patch's bytes.
+__device__ __forceinline__ uint4 fan_paid(const uint4 &piece, uint32_t q, const FanPay &p) {
+    return fan_paid_one(fan_paid_one(piece, q, p.on0, p.at0, p.v00, p.v01, p.c), q, p.on1, p.at1, p.v10, p.v11, p.c);
+}
+struct FanPayReader { // the walk's bytes: the source's, behind the entry's two patches
+    FanAstReader rd;
+    FanPay p;
+    __device__ __forceinline__ int operator()(int i) const {
+        return fanout_pay_byte(fanout_pay_byte(rd(i), i, p.at0, p.v00, p.v01, p.c), i, p.at1, p.v10, p.v11, p.c);
+    }
+};
+
+__global__ __launch_bounds__(kGatherBlock) void k_fanout_pay(FanoutArgs f, const uint4 *rewrite, const uint2 *stamp,
+                                                             const uint2 *pay) {
+    __shared__ uint4 rows[kGatherBlock / 64][2u * kFanAstLanes];
+    const uint32_t lane = threadIdx.x & 63u;
+    uint4 *row = rows[threadIdx.x >> 6];
+    const uint32_t waves = gridDim.x * (kGatherBlock / 64);
+    for (uint32_t j = 2u * (blockIdx.x * (kGatherBlock / 64) + (threadIdx.x >> 6)); j < f.n; j += 2u * waves) {
+        const bool two = j + 1u < f.n;
+        const FanEntry ea = fan_entry(f, j), eb = fan_entry(f, two ? j + 1u : j);
+        if (lane == 0u) {
+            f.len[j] = (uint32_t)ea.job.len_out;
+            f.flags_out[j] = ea.job.flags_out;
+            if (two) {
+                f.len[j + 1u] = (uint32_t)eb.job.len_out;
+                f.flags_out[j + 1u] = eb.job.flags_out;
+            }
+            const unsigned long long sk = (unsigned long long)(ea.job.by_source + (two ? eb.job.by_source : 0));
+            if (sk) atomicAdd(f.skipped, sk);
+        }
+        const uint32_t wa = (uint32_t)ea.job.copy_bytes / 16u, wb = two ? (uint32_t)eb.job.copy_bytes / 16u : 0u;
+        if ((wa | wb) == 0u) continue; // no work: no pointer is formed
+        const uint32_t ja = wa ? j : j + 1u, jb = wb ? j + 1u : j;
+        const uint4 *fa = reinterpret_cast<const uint4 *>(f.src_seg + (wa ? ea.src_at : eb.src_at));
+        const uint4 *fb = reinterpret_cast<const uint4 *>(f.src_seg + (wb ? eb.src_at : ea.src_at));
+        uint4 *ta = reinterpret_cast<uint4 *>(f.seg + f.off[ja]);
+        uint4 *tb = reinterpret_cast<uint4 *>(f.seg + f.off[jb]);
+        // each entry's own records, by its own index (j and j + 1 move with the stride loop)
+        uint4 ra = {}, rb = {};
+        bool pa = false, pb = false;
+        if (rewrite) {
+            ra = rewrite[j];
+            rb = rewrite[two ? j + 1u : j];
+            pa = fan_patches(ea, ra);
+            pb = two && fan_patches(eb, rb);
+        }
+        // an entry without bytes, or a second entry that is not there, has bound 0: no patch of its record is on
+        const FanPay ya = fan_pay(pay[j], wa ? fanout_pay_bound(ea.job, ea.src_len, ea.src_cap, ea.dst_cap) : 0);
+        const FanPay yb =
+            fan_pay(pay[two ? j + 1u : j], wb ? fanout_pay_bound(eb.job, eb.src_len, eb.src_cap, eb.dst_cap) : 0);
+        uint2 sa = {}, sb = {};
+        int ata = -1, atb = -1;
+        if (stamp) { // the same for every lane of the grid
+            sa = stamp[j];
+            sb = stamp[two ? j + 1u : j];
+            const int ca = wa ? fan_ast_wanted(ea, sa) : 0, cb = wb ? fan_ast_wanted(eb, sb) : 0;
+            if ((ca | cb) != 0) { // the same for every lane of the wave
+                walk_sync();      // the previous pair's walk has read the row
+                const uint32_t piece = lane & (kFanAstLanes - 1u);
+                if (lane < kFanAstLanes) {
+                    if (ca && piece < wa) row[lane] = fa[piece];
+                } else if (lane < 2u * kFanAstLanes) {
+                    if (cb && piece < wb) row[lane] = fb[piece];
+                }
+                walk_sync();
+                int at = -1;
+                if (lane == 0u && ca) {
+                    const FanPayReader rd{{reinterpret_cast<const uint8_t *>(row), reinterpret_cast<const uint8_t *>(fa),
+                                           (int)min(kFanAstPrefix, 16u * wa)},
+                                          ya};
+                    at = fanout_ast_find(rd, ea.job, ea.src_len, ea.src_cap, ea.dst_cap, (sa.y >> 8) & 0xFFu,
+                                         sa.y & 0xFFu);
+                } else if (lane == 1u && cb) {
+                    const FanPayReader rd{{reinterpret_cast<const uint8_t *>(row + kFanAstLanes),
+                                           reinterpret_cast<const uint8_t *>(fb), (int)min(kFanAstPrefix, 16u * wb)},
+                                          yb};
+                    at = fanout_ast_find(rd, eb.job, eb.src_len, eb.src_cap, eb.dst_cap, (sb.y >> 8) & 0xFFu,
+                                         sb.y & 0xFFu);
+                }
+                ata = __builtin_amdgcn_readlane(at, 0);
+                atb = __builtin_amdgcn_readlane(at, 1);
+            }
+        }
+        for (uint32_t o = lane; o < max(wa, wb); o += 128u) {
+            const bool a0 = o < wa, a1 = o + 64u < wa, b0 = o < wb, b1 = o + 64u < wb;
+            uint4 x0, x1, y0, y1;
+            if (a0) x0 = fa[o];
+            if (a1) x1 = fa[o + 64u];
+            if (b0) y0 = fb[o];
+            if (b1) y1 = fb[o + 64u];
+            // The trip's one wait, said here for every lane: the stores' blocks are long enough for the compiler
+            // to branch around them where no lane stores, and a wait inside them alone would leave a path with a
+            // load in flight, which it then guards with a wait in front of every load of the next trip.
+            __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0), expcnt and lgkmcnt left alone
+            if (a0) ta[o] = fan_stamped(fan_paid(fan_patched(x0, ra, pa && o == 0u), o, ya), o, ata, sa.x);
+            if (a1) ta[o + 64u] = fan_stamped(fan_paid(x1, o + 64u, ya), o + 64u, ata, sa.x);
+            if (b0) tb[o] = fan_stamped(fan_paid(fan_patched(y0, rb, pb && o == 0u), o, yb), o, atb, sb.x);
+            if (b1) tb[o + 64u] = fan_stamped(fan_paid(y1, o + 64u, yb), o + 64u, atb, sb.x);
+        }
+    }
+}
+
+hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s, const void *rewrite, const void *stamp,
+                         const void *pay) {
     if (f.n == 0) return hipSuccess;
     const uint32_t wgs = std::min<uint32_t>((f.n + 7u) / 8u, 4096u); // two entries per wave
-    if (stamp)
+    if (pay)
+        hipLaunchKernelGGL(k_fanout_pay, dim3(wgs), dim3(kGatherBlock), 0, s, f, static_cast<const uint4 *>(rewrite),
+                           static_cast<const uint2 *>(stamp), static_cast<const uint2 *>(pay));
+    else if (stamp)
         hipLaunchKernelGGL(k_fanout_ast, dim3(wgs), dim3(kGatherBlock), 0, s, f, static_cast<const uint4 *>(rewrite),
                            static_cast<const uint2 *>(stamp));
     else if (rewrite)

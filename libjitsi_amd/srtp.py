@@ -463,6 +463,46 @@ class SRTPEngine:
             None if stamp is None else stamp.data_ptr(), status.data_ptr(), n, sp)
         N.check(rc, self.h, "srtp_fanout_device_ast")
 
+    def fanout_device_pay(self, tid, src_seg, src_off, src_len, src_cap, src_idx, seg, off, length, cap, status,
+                          rewrite, stamp, pay, src_status=None, flags=None, m: Optional[int] = None,
+                          n: Optional[int] = None, stream=None) -> None:
+        """srtp_fanout_device_pay: :meth:`fanout_device_ast` with one payload
+        record per destination entry.  ``pay`` is a tensor on this engine's
+        GPU that holds n x 8 bytes, 8-byte aligned (n records of
+        ``N.FANOUT_PAYLOAD_DTYPE``: at0, b0, at1, b1), or None for
+        :meth:`fanout_device_ast` exactly; ``rewrite`` and ``stamp`` may each
+        be None either way.  A patch writes its two bytes at packet bytes
+        ``at``, ``at + 1`` of entry j's copy before the copy is protected --
+        the RTX original sequence number, rewriteRTX's
+        setOriginalSequenceNumber (ExtendedSequenceNumberInterval.java:261-284,
+        RawPacket.java:1018-1022), or the FEC header's SN base, rewriteFEC's
+        two stores (ExtendedSequenceNumberInterval.java:346-386).  It is on
+        when ``at >= 12`` and the copy holds byte ``at``; a byte the copy does
+        not hold is not written.  Patch 0, then patch 1, then the stamp."""
+        if m is None:
+            m = src_off.numel()
+        if n is None:
+            n = off.numel()
+        if rewrite is not None and rewrite.numel() * rewrite.element_size() < 16 * n:
+            raise ValueError("fanout_device_pay: rewrite holds fewer than n records")
+        if stamp is not None and stamp.numel() * stamp.element_size() < 8 * n:
+            raise ValueError("fanout_device_pay: stamp holds fewer than n records")
+        if pay is not None and pay.numel() * pay.element_size() < 8 * n:
+            raise ValueError("fanout_device_pay: pay holds fewer than n records")
+        if np.isscalar(tid):
+            tids_p, tid0 = None, int(tid)
+        else:
+            tids_p, tid0 = tid.data_ptr(), -1
+        sp = getattr(stream, "cuda_stream", stream)
+        rc = N.lib().srtp_fanout_device_pay(
+            self.h, src_seg.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), src_cap.data_ptr(),
+            None if src_status is None else src_status.data_ptr(), m, src_idx.data_ptr(), tids_p, tid0,
+            seg.data_ptr(), off.data_ptr(), length.data_ptr(), cap.data_ptr(),
+            None if flags is None else flags.data_ptr(), None if rewrite is None else rewrite.data_ptr(),
+            None if stamp is None else stamp.data_ptr(), None if pay is None else pay.data_ptr(),
+            status.data_ptr(), n, sp)
+        N.check(rc, self.h, "srtp_fanout_device_pay")
+
     def fanout_host(self, tid, src_seg: np.ndarray, src_off, src_len, src_cap, src_idx, seg: np.ndarray, off,
                     cap, src_status=None, flags=None):
         """srtp_fanout_host over numpy: only the source segment and the small
@@ -552,6 +592,53 @@ class SRTPEngine:
             None if fl is None else fl.ctypes.data, None if rw is None else rw.ctypes.data, ast.ctypes.data,
             status.ctypes.data, n)
         N.check(rc, self.h, "srtp_fanout_host_ast")
+        return length, status
+
+    def fanout_host_pay(self, tid, src_seg: np.ndarray, src_off, src_len, src_cap, src_idx, seg: np.ndarray, off,
+                        cap, src_status=None, flags=None, rewrite=None, stamp=None, pay=None):
+        """srtp_fanout_host_pay: :meth:`fanout_host_ast` with one payload
+        record per destination entry, ``pay`` a numpy structured array of n
+        records with dtype ``N.FANOUT_PAYLOAD_DTYPE`` (None:
+        :meth:`fanout_host_ast` exactly); ``rewrite`` and ``stamp`` may each be
+        None.  What a record does is :meth:`fanout_device_pay`'s
+        (ExtendedSequenceNumberInterval.java:261-284 and :346-386)."""
+        if pay is None:
+            return self.fanout_host_ast(tid, src_seg, src_off, src_len, src_cap, src_idx, seg, off, cap, src_status,
+                                        flags, rewrite, stamp)
+        assert src_seg.dtype == np.uint8 and src_seg.flags.c_contiguous
+        assert seg.dtype == np.uint8 and seg.flags.c_contiguous and seg.flags.writeable
+        src_off = np.ascontiguousarray(src_off, np.uint32)
+        src_len = np.ascontiguousarray(src_len, np.uint32)
+        src_cap = np.ascontiguousarray(src_cap, np.uint32)
+        src_idx = np.ascontiguousarray(src_idx, np.int32)
+        off = np.ascontiguousarray(off, np.uint32)
+        cap = np.ascontiguousarray(cap, np.uint32)
+        m, n = len(src_off), len(off)
+        assert len(src_len) == m and len(src_cap) == m and len(src_idx) == n and len(cap) == n
+        st_in = None if src_status is None else np.ascontiguousarray(src_status, np.int32)
+        fl = None if flags is None else np.ascontiguousarray(flags, np.uint32)
+        assert (st_in is None or len(st_in) == m) and (fl is None or len(fl) == n)
+        rw = None if rewrite is None else np.ascontiguousarray(rewrite, N.FANOUT_REWRITE_DTYPE)
+        ast = None if stamp is None else np.ascontiguousarray(stamp, N.FANOUT_AST_DTYPE)
+        py = np.ascontiguousarray(pay, N.FANOUT_PAYLOAD_DTYPE)
+        if len(py) < n:
+            raise ValueError("fanout_host_pay: pay holds fewer than n records")
+        assert (rw is None or len(rw) == n) and (ast is None or len(ast) == n)
+        if np.isscalar(tid):
+            tids_p, tid0 = None, int(tid)
+        else:
+            tids = np.ascontiguousarray(tid, np.int32)
+            assert len(tids) == n
+            tids_p, tid0 = tids.ctypes.data, -1
+        length = np.zeros(n, np.uint32)
+        status = np.zeros(n, np.int32)
+        rc = N.lib().srtp_fanout_host_pay(
+            self.h, src_seg.ctypes.data, src_seg.nbytes, src_off.ctypes.data, src_len.ctypes.data,
+            src_cap.ctypes.data, None if st_in is None else st_in.ctypes.data, m, src_idx.ctypes.data, tids_p,
+            tid0, seg.ctypes.data, seg.nbytes, off.ctypes.data, length.ctypes.data, cap.ctypes.data,
+            None if fl is None else fl.ctypes.data, None if rw is None else rw.ctypes.data,
+            None if ast is None else ast.ctypes.data, py.ctypes.data, status.ctypes.data, n)
+        N.check(rc, self.h, "srtp_fanout_host_pay")
         return length, status
 
     def fanout_stats(self) -> dict:
@@ -1422,6 +1509,68 @@ def fan_out_ast(pkts: Sequence[Optional[RawPacket]], transformers: Sequence[_SRT
     return _fan_out(pkts, transformers, rewriters, exclusion, stampers)
 
 
+def fec_sn_bytes(sn: int):
+    """The two bytes rewriteFEC stores at ``off + 2`` and ``off + 3`` of an FEC
+    header for the rewritten SN base ``sn``
+    (ExtendedSequenceNumberInterval.java:383-384), **as Java evaluates them**:
+    ``(byte) (snRewritenBase & 0xff00 >> 8)`` shifts before it masks, so it is
+    ``snRewritenBase & 0xff`` -- both bytes are the low byte of ``sn``, and
+    ``fec_sn_bytes(0x1234) == (0x34, 0x34)``.  :func:`fan_out_pay` writes what
+    the reference writes; a caller who wants the big-endian number, or any
+    other bytes, fills ``N.FANOUT_PAYLOAD_DTYPE`` records and calls
+    :meth:`SRTPEngine.fanout_host_pay`: the record carries bytes and has no
+    opinion."""
+    sn = int(sn)
+    return (sn & (0xFF00 >> 8)) & 0xFF, sn & 0x00FF
+
+
+def fan_out_pay(pkts: Sequence[Optional[RawPacket]], transformers: Sequence[_SRTPBase], rewriters, stampers,
+                exclusion=None):
+    """:func:`fan_out_ast` for streams that carry RTX or FEC.  Besides the four
+    header fields, ExtendedSequenceNumberInterval.rewriteRTP
+    (ExtendedSequenceNumberInterval.java:163-229) writes two per-peer values
+    into the payload before the SRTP transformer sees the packet, and a
+    rewriter's mapping may carry them as two more keys:
+
+    ``osn``: an int, the peer's rewritten number of the original packet.  It is
+    written big-endian at ``pkt.getHeaderLength()`` of the source packet:
+    rewriteRTX's ``setOriginalSequenceNumber`` (:261-284), which is
+    ``writeShort(getHeaderLength(), sn)`` (RawPacket.java:1018-1022, 1334-1337).
+
+    ``fec``: ``(off, sn)``, where ``off`` is the FEC header's offset from the
+    packet's first byte (for a RED packet the matching block's, which the
+    host's block walk finds).  The bytes at ``off + 2`` and ``off + 3`` become
+    :func:`fec_sn_bytes` ``(sn)``: rewriteFEC's two stores (:346-386; rewriteRED,
+    :307-333).
+
+    Both may appear together (an FEC packet inside RTX): ``fec`` is written
+    first, then ``osn``, rewriteRTP's order.  A header length or offset that
+    does not fit 16 bits, or lies below byte 12, raises ``ValueError``.  The
+    bytes are written into the copies on the GPU (srtp_fanout_host_pay) before
+    they are protected; a byte the copy does not hold is not written.
+    Everything else is :func:`fan_out_ast`'s."""
+    transformers, rewriters, stampers = list(transformers), list(rewriters), list(stampers)
+    if len(rewriters) != len(transformers):
+        raise ValueError("fan_out_pay: one rewriter (or None) per transformer")
+    if len(stampers) != len(transformers):
+        raise ValueError("fan_out_pay: one stamper (or None) per transformer")
+    return _fan_out(pkts, transformers, rewriters, exclusion, stampers, payload=True)
+
+
+def _pay_one(pay, j, r, p):
+    """Entry j's payload record from the rewriter's mapping r: fec is patch 0, osn patch 1."""
+    if "fec" in r:
+        off, sn = r["fec"]
+        if not 12 <= int(off) <= 0xFFFF - 2:
+            raise ValueError("fan_out_pay: an FEC header at offset %r" % (off,))
+        pay["at0"][j], pay["b0"][j] = int(off) + 2, fec_sn_bytes(sn)
+    if "osn" in r:
+        at = int(p.getHeaderLength())
+        if not 12 <= at <= 0xFFFF:
+            raise ValueError("fan_out_pay: a header length of %d" % at)
+        pay["at1"][j], pay["b1"][j] = at, ((int(r["osn"]) >> 8) & 0xFF, int(r["osn"]) & 0xFF)
+
+
 _REWRITE_FIELDS = (("ssrc", N.REWRITE_SSRC, 0xFFFFFFFF), ("seq", N.REWRITE_SEQ, 0xFFFF),
                    ("timestamp", N.REWRITE_TIMESTAMP, 0xFFFFFFFF), ("pt", N.REWRITE_PT, 0x7F))
 
@@ -1439,7 +1588,7 @@ def _stamp_one(stamp, j, g, p):
     stamp["id"][j], stamp["value"][j], stamp["on"][j] = int(ext_id), int(value) & 0x00FFFFFF, 1
 
 
-def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None):
+def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None, payload=False):
     pkts, transformers = list(pkts), list(transformers)
     out = [[None] * len(pkts) for _ in transformers]
     if not pkts or not transformers:
@@ -1462,12 +1611,14 @@ def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None):
             if x is t or (t.packetPredicate is not None and pkts[i] is not None
                           and not t.packetPredicate(pkts[i])):
                 flags[i * T + k] |= N.PKT_FLAG_SKIP
-    rewrite = stamp = None
+    rewrite = stamp = pay = None
     if stampers is not None and any(g is not None for g in stampers):
         stamp = np.zeros(len(pkts) * T, N.FANOUT_AST_DTYPE)
     if (rewriters is not None and any(f is not None for f in rewriters)) or stamp is not None:
         if rewriters is not None and any(f is not None for f in rewriters):
             rewrite = np.zeros(len(pkts) * T, N.FANOUT_REWRITE_DTYPE)
+            if payload:
+                pay = np.zeros(len(pkts) * T, N.FANOUT_PAYLOAD_DTYPE)
         for i, p in enumerate(pkts):  # doWrite's order
             for k in range(T):
                 j = i * T + k
@@ -1482,9 +1633,11 @@ def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None):
                 if r is None:
                     flags[j] |= N.PKT_FLAG_SKIP
                     continue
-                unknown = set(r) - {name for name, _, _ in _REWRITE_FIELDS}
+                unknown = set(r) - {name for name, _, _ in _REWRITE_FIELDS} - ({"osn", "fec"} if payload else set())
                 if unknown:
                     raise ValueError("fan_out_rw: a rewriter returned %s" % sorted(unknown))
+                if payload:
+                    _pay_one(pay, j, r, p)
                 for name, bit, lim in _REWRITE_FIELDS:
                     if name in r:
                         rewrite[name][j] = int(r[name]) & lim
@@ -1495,8 +1648,10 @@ def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None):
     if int(off[-1] + step[-1]) >= 1 << 32:
         raise ValueError("fan_out: more than 4 GiB of copies")
     seg = np.zeros(int(off[-1] + step[-1]), np.uint8)
-    ln, st = eng.fanout_host_ast(tids, src_seg, src_off, src_len, src_cap, src_idx, seg, off.astype(np.uint32), cap,
-                                 src_status, flags, rewrite, stamp)
+    if pay is not None and not (pay["at0"].any() or pay["at1"].any()):
+        pay = None  # no rewriter named a payload value: fan_out_ast's call
+    ln, st = eng.fanout_host_pay(tids, src_seg, src_off, src_len, src_cap, src_idx, seg, off.astype(np.uint32), cap,
+                                 src_status, flags, rewrite, stamp, pay)
     for j in np.nonzero(st == N.STATUS_OK)[0]:
         i, k = divmod(int(j), T)
         o = int(off[j])

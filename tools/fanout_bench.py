@@ -33,6 +33,16 @@
             calls (stamp records only) and nothing else (a trace of
             k_fanout_ast); --stamp-records off | miss takes the walk, or the
             stamp, out of that trace.
+  --payload payload patches (srtp_fanout_*_pay): the --stamp sources (a header
+            of 28 bytes); every entry's record has both patches on, an FEC SN
+            base at bytes 42..43 (patch 0) and the RTX OSN at bytes 28..29
+            (patch 1), with bytes of its own per call.  Device route, n = 2^18,
+            N = 8: fanout_device_pay with patch records only, and with rewrite
+            and stamp records as well, against fanout_device_ast (stamp only),
+            fanout_device_rw and fanout_device over the same sources, the five
+            alternating call by call, HIP events.  With --once: three
+            fanout_device_pay calls (patch records only) and nothing else (a
+            trace of k_fanout_pay).
   --plain   fanout_device of the --device shape and nothing else, 5 warm-up and
             20 timed calls (one side of a comparison between two builds of the
             library, a process each).
@@ -335,7 +345,7 @@ def device_setup(eng, n, fan):
     return w
 
 
-def timed_fanout(eng, w, rewrite, stamp=None):
+def timed_fanout(eng, w, rewrite, stamp=None, pay=None):
     """One fan-out of fresh sources on the stream, between two HIP events: ms."""
     import torch
     w["src"].advance()
@@ -348,11 +358,18 @@ def timed_fanout(eng, w, rewrite, stamp=None):
     if stamp is not None:
         stamp.update()
         ast = torch.from_numpy(stamp.ast.view(np.uint8)).cuda()
+    py = None
+    if pay is not None:
+        pay.update()
+        py = torch.from_numpy(pay.pay.view(np.uint8)).cuda()
     torch.cuda.synchronize()
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     with torch.cuda.stream(w["stream"]):
         a.record()
-        if ast is not None:
+        if py is not None:
+            eng.fanout_device_pay(w["tids"], s_seg, w["s_off"], w["s_len"], w["s_cap"], w["idx"], w["seg"], w["off"],
+                                  w["ln"], w["cap"], w["st"], rw, ast, py, stream=w["stream"])
+        elif ast is not None:
             eng.fanout_device_ast(w["tids"], s_seg, w["s_off"], w["s_len"], w["s_cap"], w["idx"], w["seg"], w["off"],
                                   w["ln"], w["cap"], w["st"], rw, ast, stream=w["stream"])
         elif rw is None:
@@ -482,6 +499,54 @@ def stamp_host_case(eng, n, fan):
             "h2d_bytes_expand": n * DST_STRIDE + 4 * 4 * n, "verdict": verdict(a, b)}
 
 
+PAY_DTYPE = np.dtype([("at0", "<u2"), ("b0", "u1", (2,)), ("at1", "<u2"), ("b1", "u1", (2,))])  # srtp_fanout_payload
+FEC_AT, OSN_AT = 42, 28
+
+
+class Payloads:
+    """One record per destination entry with both patches on; update() gives every entry new bytes."""
+
+    def __init__(self, n):
+        self.n, self.tick = n, 0
+        self.pay = np.zeros(n, PAY_DTYPE)
+        self.pay["at0"], self.pay["at1"] = FEC_AT, OSN_AT
+        self.update()
+
+    def update(self):
+        self.tick += 1
+        v = (np.arange(self.n, dtype=np.uint64) * 2246822519 + 131 * self.tick) & 0xFFFFFFFF
+        self.pay["b0"] = np.stack([v & 0xFF, v & 0xFF], 1)  # rewriteFEC stores the low byte twice
+        self.pay["b1"] = np.stack([(v >> 24) & 0xFF, (v >> 16) & 0xFF], 1)
+
+
+def payload_device_case(eng, n, fan):
+    w = device_setup(eng, n, fan)
+    w["src"].with_extension()
+    tg, sp, py = Targets(w["src"], w["src_idx"], fan), Stamps(n), Payloads(n)
+    t = {"fanout_device_pay_patches_only": [], "fanout_device_pay_all_three_records": [],
+         "fanout_device_ast_stamp_only": [], "fanout_device_rw_all_four_fields": [], "fanout_device": []}
+    pick = slice(None, None, max(1, n // 64))
+    for it in range(WARM + TIMED):
+        for name, (rw, st, pp) in zip(t, ((None, None, py), (tg, sp, py), (None, sp, None), (tg, None, None),
+                                          (None, None, None))):
+            x = timed_fanout(eng, w, rw, st, pp)
+            if st is not None:  # the stamp is in the clear; the patched bytes are payload and leave enciphered
+                got = w["seg"].view(n, DST_STRIDE)[pick, STAMP_AT:STAMP_AT + 3].cpu().numpy()
+                assert (got == sp.bytes3()[pick]).all()
+            if it >= WARM:
+                t[name].append(x)
+    res = {k: pct(v) for k, v in t.items()}
+    med = {k: v["median_ms"] for k, v in res.items()}
+    spread = max(x["p90_ms"] - x["p10_ms"] for x in res.values())
+    res.update({"n": n, "N": fan, "m": w["m"],
+                "pay_minus_plain_ms": med["fanout_device_pay_patches_only"] - med["fanout_device"],
+                "rw_minus_plain_ms": med["fanout_device_rw_all_four_fields"] - med["fanout_device"],
+                "ast_minus_plain_ms": med["fanout_device_ast_stamp_only"] - med["fanout_device"],
+                "pay_all_three_minus_plain_ms": med["fanout_device_pay_all_three_records"] - med["fanout_device"],
+                "widest_p90_minus_p10_ms": spread, "record_bytes_read": 8 * n, "bytes_written": n * LEN})
+    return res
+
+
 def plain_device_case(eng, n, fan):
     w = device_setup(eng, n, fan)
     t = [timed_fanout(eng, w, None) for _ in range(WARM + TIMED)][WARM:]
@@ -496,13 +561,14 @@ def main():
     ap.add_argument("--rewrite", action="store_true")
     ap.add_argument("--plain", action="store_true")
     ap.add_argument("--stamp", action="store_true")
+    ap.add_argument("--payload", action="store_true")
     ap.add_argument("--stamp-records", choices=("on", "off", "miss"), default="on",
                     help="with --once --stamp: every record on (default), off, or on under the ID of no element")
     ap.add_argument("--log2n-host", type=int, default=16)
     ap.add_argument("--log2n-device", type=int, default=18)
     ap.add_argument("--out")
     args = ap.parse_args()
-    if args.device or args.once or args.rewrite or args.plain or args.stamp:
+    if args.device or args.once or args.rewrite or args.plain or args.stamp or args.payload:
         import torch  # asked before the engine library initialises HIP: torch caches its first answer
         assert torch.cuda.is_available()
     eng = SRTPEngine(device=0, max_contexts=1 << 19, max_factories=256, max_transformers=256,
@@ -512,7 +578,14 @@ def main():
     if args.host:
         res["host"] = [host_case(eng, prof, 1 << args.log2n_host, fan)
                        for prof in ("AES_CM_128_HMAC_SHA1_80", "AEAD_AES_128_GCM") for fan in (1, 2, 4, 8, 16)]
-    if args.once and args.stamp:  # three fanout_device_ast calls and nothing else (a trace of k_fanout_ast)
+    if args.once and args.payload:  # three fanout_device_pay calls and nothing else (a trace of k_fanout_pay)
+        w = device_setup(eng, 1 << args.log2n_device, 8)
+        w["src"].with_extension()
+        py = Payloads(1 << args.log2n_device)
+        res["device"] = {"once_pay_ms": [timed_fanout(eng, w, None, None, py) for _ in range(3)]}
+    elif args.payload:
+        res["payload_device"] = payload_device_case(eng, 1 << args.log2n_device, 8)
+    elif args.once and args.stamp:  # three fanout_device_ast calls and nothing else (a trace of k_fanout_ast)
         w = device_setup(eng, 1 << args.log2n_device, 8)
         w["src"].with_extension()
         sp = Stamps(1 << args.log2n_device, args.stamp_records)
