@@ -94,6 +94,8 @@ EXPORTED = [
     "srtp_fanout_device_rw", "srtp_fanout_host_rw", "srtp_fanout_rewrite_job",
     "srtp_fanout_device_ast", "srtp_fanout_host_ast", "srtp_fanout_ast_job",
     "srtp_fanout_device_pay", "srtp_fanout_host_pay", "srtp_fanout_pay_job",
+    "srtp_transform_device_lvl", "srtp_transform_host_lvl", "srtp_engine_audio_level_stats",
+    "srtp_audio_level_job",
 ]
 STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 
@@ -101,7 +103,7 @@ STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 # Sources that decide what the crypto kernels execute: the key that ties
 # committed PMC counters (profiles/pmc_traffic.json) to the build they measured.
 KERNEL_SOURCES = ["srtp_kernels.hip", "aes_rounds_asm.inc", "srtp_kernels.h", "srtp_types.h", "engine.cpp",
-                  "gcm_job.h", "fanout_job.h", "bundle_plan.h"]
+                  "gcm_job.h", "fanout_job.h", "bundle_plan.h", "audio_level_job.h"]
 
 
 def kernel_source_sha16() -> str:
@@ -228,6 +230,18 @@ class FanoutPayload(C.Structure):
 
 # numpy's view of an array of srtp_fanout_payload (fanout_host_pay)
 FANOUT_PAYLOAD_DTYPE = np.dtype([("at0", "<u2"), ("b0", "u1", (2,)), ("at1", "<u2"), ("b1", "u1", (2,))])
+
+
+class AudioLevelStats(C.Structure):
+    """srtp_audio_level_stats (include/srtp_mi355x.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "entries_read", "levels_found", "silent")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+AUDIO_LEVEL_NONE = -128   # Byte.MIN_VALUE: the packet carries no level
+AUDIO_LEVEL_MUTED = 127   # RFC 6464: a muted source (flagged PKT_FLAG_SILENCE)
 
 DTLS_AEAD = 0x1
 GCM_HDR_THROW = -0x80000000
@@ -391,6 +405,10 @@ def lib() -> C.CDLL:
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.srtp_engine_fanout_stats.argtypes = [vp, C.POINTER(FanoutStats)]
     L.srtp_fanout_job.argtypes = [i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutPlan)]
+    L.srtp_transform_device_lvl.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, C.c_uint8, vp, vp, u32, vp]
+    L.srtp_transform_host_lvl.argtypes = [vp, vp, i32, vp, C.c_size_t, vp, vp, vp, vp, vp, C.c_uint8, vp, vp, u32]
+    L.srtp_engine_audio_level_stats.argtypes = [vp, C.POINTER(AudioLevelStats)]
+    L.srtp_audio_level_job.argtypes = [vp, i32, i32, u32, C.c_uint8, C.POINTER(C.c_int8), C.POINTER(C.c_uint32)]
     L.srtp_trailer_room.argtypes = [i32]
     L.srtp_trailer_room.restype = i32
     L.srtp_engine_trailer_room.argtypes = [vp]

@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "../../include/srtp_mi355x.h"
+#include "audio_level_job.h"
 #include "fanout_job.h"
 #include "gcm_job.h"
 #include "host_crypto.h"
@@ -122,6 +123,18 @@ struct srtp_engine {
     uint32_t *hs_off = nullptr, *hs_len = nullptr, *hs_cap = nullptr;
     int32_t *hs_status = nullptr, *hs_idx = nullptr;
     uint64_t fan_calls = 0, fan_sources = 0, fan_destinations = 0, fan_src_bytes = 0;
+
+    // audio levels (srtp_transform_*_lvl): the engine-owned flags words
+    // k_audio_level writes and the unprotect chain reads, its counters (rows of
+    // entries read, levels found, flagged silent), and srtp_transform_host_lvl's
+    // staging of the IDs and the levels
+    uint32_t *lvl_flags = nullptr;
+    uint32_t lvl_n = 0;
+    unsigned long long *d_lvl_stats = nullptr;
+    uint8_t *h_ext_ids = nullptr;
+    int8_t *h_level = nullptr;
+    uint32_t h_lvl_n = 0;
+    uint64_t lvl_calls = 0;
 
     // optional per-stage timing (HIP events on the bundle stream)
     bool timing = false;
@@ -617,7 +630,8 @@ void srtp_engine_destroy(srtp_engine *e) {
     void *ptrs[] = {e->d_keysets, e->d_extkeys, e->d_tfkeys, e->d_skkeys, e->d_gcmkeys, e->d_gcmpow, e->d_factories, e->d_transformers, e->d_ctx_keys, e->d_ctx,
                     e->d_far, e->e_min, e->ctl, e->d_count, e->d_counters, e->h_seg, e->h_off, e->h_len,
                     e->h_cap, e->h_flags, e->h_status, e->h_tids, e->fan_flags, e->d_fan_skipped, e->hs_seg,
-                    e->hs_off, e->hs_len, e->hs_cap, e->hs_status, e->hs_idx, e->hs_rw, e->hs_ast, e->hs_pay};
+                    e->hs_off, e->hs_len, e->hs_cap, e->hs_status, e->hs_idx, e->hs_rw, e->hs_ast, e->hs_pay,
+                    e->lvl_flags, e->d_lvl_stats, e->h_ext_ids, e->h_level};
     for (void *p : ptrs) dfree(p);
     if (e->ev_last) (void)hipEventDestroy(e->ev_last);
     if (e->ev_dev) (void)hipEventDestroy(e->ev_dev);
@@ -1342,6 +1356,136 @@ int srtp_fanout_pay_job(int32_t src_idx, int32_t m, int32_t src_len, int32_t src
     words_out[1] = p.w1;
     words_out[2] = p.w2;
     words_out[3] = p.w3;
+    return SRTP_OK;
+}
+
+// ------------------------------------------------------------- audio levels
+// k_audio_level in front of the unprotect chain, both on `s`.  The flags words
+// the chain reads are the engine's (lvl_flags), so the stage waits, like a
+// bundle, for the previous bundle of another stream.
+static int lvl_locked(srtp_engine *e, const int32_t *tids, int32_t tid, uint8_t *seg, const uint32_t *off,
+                      uint32_t *len, const uint32_t *cap, const uint32_t *flags, const uint8_t *ext_ids,
+                      uint8_t ext_id, int8_t *level, int32_t *status, uint32_t n, hipStream_t s, bool dev_event) {
+    int rc = check_buffers(e, {seg, off, len, cap, level, status});
+    if (rc == SRTP_OK) rc = check_size(e, n);
+    if (rc == SRTP_OK) rc = check_tid(e, tids != nullptr, tid);
+    if (rc == SRTP_OK) rc = ensure_scratch(e, n);
+    if (rc != SRTP_OK) return rc;
+    if (n > e->lvl_n) {
+        if (e->have_last) { // the old flags words may still be read by an enqueued bundle
+            rc = quiesce(e);
+            if (rc != SRTP_OK) return rc;
+        }
+        rc = grow_staging(e, &e->lvl_n, std::max<uint32_t>(n, 1024), &e->lvl_flags);
+        if (rc != SRTP_OK) return rc;
+    }
+    if (!e->d_lvl_stats) {
+        HIPCHK(e, dalloc(&e->d_lvl_stats, kLvlStatReplicas * kLvlStatStride));
+        HIPCHK(e, hipMemset(e->d_lvl_stats, 0, kLvlStatReplicas * kLvlStatStride * sizeof(unsigned long long)));
+    }
+    if (e->have_last && e->last_stream != s) HIPCHK(e, hipStreamWaitEvent(s, last_event(e), 0));
+    AudioLevelArgs a{};
+    a.seg = seg; a.off = off; a.len = len; a.cap = cap; a.flags = flags;
+    a.ext_ids = ext_ids; a.ext_id = ext_id;
+    a.level = level;
+    a.flags_out = e->lvl_flags;
+    a.stats = e->d_lvl_stats;
+    a.n = n;
+    HIPCHK(e, launch_audio_level(a, s));
+    rc = transform_locked(e, 1, tids, tid, seg, off, len, cap, e->lvl_flags, status, n, s, -1, dev_event);
+    if (rc != SRTP_OK) return rc;
+    e->lvl_calls++;
+    return SRTP_OK;
+}
+
+int srtp_transform_device_lvl(srtp_engine *e, const int32_t *tids, int32_t tid, uint8_t *seg, const uint32_t *off,
+                              uint32_t *len, const uint32_t *cap, const uint32_t *flags, const uint8_t *ext_ids,
+                              uint8_t ext_id, int8_t *level, int32_t *status, uint32_t n, void *stream) {
+    if (!e) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (n == 0) return SRTP_OK;
+    GUARD(e);
+    return lvl_locked(e, tids, tid, seg, off, len, cap, flags, ext_ids, ext_id, level, status, n,
+                      (hipStream_t)stream, true);
+}
+
+int srtp_transform_host_lvl(srtp_engine *e, const int32_t *tids, int32_t tid, uint8_t *seg, size_t seg_bytes,
+                            const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                            const uint8_t *ext_ids, uint8_t ext_id, int8_t *level, int32_t *status, uint32_t n) {
+    if (!e) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (n == 0) return SRTP_OK;
+    int vr = check_buffers(e, {seg, off, len, cap, level, status});
+    if (vr == SRTP_OK) vr = validate_regions(e, off, cap, n, seg_bytes);
+    if (vr != SRTP_OK) return vr;
+    GUARD(e);
+    hipStream_t s = e->stream;
+    int hrc = ensure_host_staging(e, seg_bytes, n);
+    if (hrc != SRTP_OK) return hrc;
+    if (n > e->h_lvl_n) {
+        if (e->have_last) { // the staged IDs and levels may still be in use by an enqueued bundle
+            hrc = quiesce(e);
+            if (hrc != SRTP_OK) return hrc;
+        }
+        hrc = grow_staging(e, &e->h_lvl_n, n, &e->h_ext_ids, &e->h_level);
+        if (hrc != SRTP_OK) return hrc;
+    }
+    HIPCHK(e, hipMemcpyAsync(e->h_seg, seg, seg_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->h_off, off, n * 4ull, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->h_len, len, n * 4ull, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->h_cap, cap, n * 4ull, hipMemcpyHostToDevice, s));
+    if (flags) HIPCHK(e, hipMemcpyAsync(e->h_flags, flags, n * 4ull, hipMemcpyHostToDevice, s));
+    if (tids) HIPCHK(e, hipMemcpyAsync(e->h_tids, tids, n * 4ull, hipMemcpyHostToDevice, s));
+    if (ext_ids) HIPCHK(e, hipMemcpyAsync(e->h_ext_ids, ext_ids, n, hipMemcpyHostToDevice, s));
+    int rc = lvl_locked(e, tids ? e->h_tids : nullptr, tid, e->h_seg, e->h_off, e->h_len, e->h_cap,
+                        flags ? e->h_flags : nullptr, ext_ids ? e->h_ext_ids : nullptr, ext_id, e->h_level,
+                        e->h_status, n, s, false);
+    if (rc != SRTP_OK) return rc;
+    HIPCHK(e, hipMemcpyAsync(seg, e->h_seg, seg_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(len, e->h_len, n * 4ull, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(status, e->h_status, n * 4ull, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(level, e->h_level, n, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    return SRTP_OK;
+}
+
+int srtp_engine_audio_level_stats(srtp_engine *e, srtp_audio_level_stats *out) {
+    if (!e || !out) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    memset(out, 0, sizeof *out);
+    out->calls = e->lvl_calls;
+    if (!e->d_lvl_stats) return SRTP_OK; // no _lvl call yet
+    GUARD(e);
+    int rc = quiesce(e);
+    if (rc != SRTP_OK) return rc;
+    unsigned long long st[kLvlStatReplicas * kLvlStatStride];
+    HIPCHK(e, hipMemcpy(st, e->d_lvl_stats, sizeof st, hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < kLvlStatReplicas; r++) { // a row per group of waves (k_audio_level)
+        out->entries_read += st[r * kLvlStatStride + 0];
+        out->levels_found += st[r * kLvlStatStride + 1];
+        out->silent += st[r * kLvlStatStride + 2];
+    }
+    return SRTP_OK;
+}
+
+namespace {
+struct LevelBytes { // the caller's packet as audio_level_find reads it
+    const uint8_t *pkt;
+    int bound;
+    int operator()(int i) const { return i >= 0 && i < bound ? pkt[i] : 0; }
+};
+} // namespace
+
+int srtp_audio_level_job(const uint8_t *pkt, int32_t len, int32_t cap, uint32_t flags, uint8_t ext_id,
+                         int8_t *level, uint32_t *flags_out) {
+    if (!level || !flags_out) return SRTP_EINVAL;
+    static_assert(SRTP_PKT_FLAG_SKIP == kLvlFlagSkip && SRTP_PKT_FLAG_SILENCE == kLvlFlagSilence,
+                  "audio_level_job.h restates these constants");
+    const int B = audio_level_wanted(flags, len, cap, ext_id);
+    if (B != 0 && !pkt) return SRTP_EINVAL;
+    const int lv = B != 0 ? audio_level_find(LevelBytes{pkt, B}, B, ext_id) : kLvlNone;
+    *level = (int8_t)lv;
+    *flags_out = audio_level_flags(flags, lv);
     return SRTP_OK;
 }
 

@@ -188,6 +188,27 @@ struct FanoutArgs {
 // instances are the ones that use LDS.
 hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s, const void *rewrite = nullptr,
                          const void *stamp = nullptr, const void *pay = nullptr);
+// srtp_transform_device_lvl: in front of the unprotect chain, entry j's
+// ssrc-audio-level is read and its flags word made (k_audio_level, the rule in
+// audio_level_job.h): level[j] = the level (0..127) or -128, flags_out[j] =
+// the caller's flags, with SILENCE for level 127.  Whether an entry is read is
+// decided from flags, len, cap and its ID before any pointer into the segment
+// is formed.  stats: kLvlStatReplicas rows of kLvlStatStride words (64 bytes);
+// a wave adds its entries read, levels found and entries flagged to words 0..2
+// of one row, and the host sums the rows.
+constexpr uint32_t kLvlStatReplicas = 64, kLvlStatStride = 8;
+struct AudioLevelArgs {
+    const uint8_t *seg;
+    const uint32_t *off, *len, *cap; // [n]
+    const uint32_t *flags;           // [n] the caller's, may be null
+    const uint8_t *ext_ids;          // [n] may be null -> ext_id
+    int32_t ext_id;                  // 0..255
+    int8_t *level;                   // [n] out
+    uint32_t *flags_out;             // [n] out
+    unsigned long long *stats;       // [kLvlStatReplicas][kLvlStatStride]
+    uint32_t n;
+};
+hipError_t launch_audio_level(const AudioLevelArgs &a, hipStream_t s);
 // unprotect: statuses/lengths out; undo/redo the rare speculation misses (after the walk)
 hipError_t launch_unprotect_fix(const BundleArgs &a, hipStream_t s);
 // AES-F8 packets after the final statuses: protect (F8 + HMAC + trailer) or

@@ -63,6 +63,7 @@
 
 
 #include "../../include/srtp_mi355x.h"
+#include "audio_level_job.h"
 #include "fanout_job.h"
 #include "gcm_job.h"
 #include "srtp_kernels.h"
@@ -7477,6 +7478,99 @@ hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s, const void *rewrite
         hipLaunchKernelGGL(k_fanout_rw, dim3(wgs), dim3(kGatherBlock), 0, s, f, static_cast<const uint4 *>(rewrite));
     else
         hipLaunchKernelGGL(k_fanout, dim3(wgs), dim3(kGatherBlock), 0, s, f);
+    return hipGetLastError();
+}
+
+// ============================================================= audio levels
+// The receive side's one engine in front of SRTP (srtp_transform_device_lvl):
+// entry j's ssrc-audio-level (RFC 6464) is read from its header extension and a
+// muted source's entry is flagged SILENCE, before the unprotect chain parses
+// the bundle.  audio_level_job.h is the rule; audio_level_wanted decides from
+// the flags, len, cap and the entry's ID alone whether the entry is read, and
+// only such an entry forms a pointer into the segment.  A wave takes 16 entries
+// per trip: four lanes per entry each park one 16-byte piece of the packet in
+// the entry's 64-byte LDS row (only pieces below B rounded up to 16, which a
+// region owns), and the entry's first lane runs audio_level_find over the row.
+// The row is the wave's own: the hand-offs are walk_sync's, reached by every
+// lane whenever the wave has an entry that is read (a wave-uniform condition).
+//
+// The reader never joins an LDS and a global pointer (k_fanout_ast's lesson:
+// the compiler made one flat address of them, and the walk a chain of flat
+// byte loads).  Inside the row every read is an LDS byte read through an
+// address-space-qualified pointer; a walk that asks for a byte past the row (a
+// CSRC list or an extension past byte 64: not what a browser sends) is told so,
+// gets 0xFF from there on -- under which the rule ends at once or within
+// B / 17 steps -- and is run again from the start over global byte loads
+// bounded by B: correct and slow.
+constexpr uint32_t kLvlPerTrip = 16;  // entries of a wave's trip
+constexpr int kLvlRowBytes = 64;      // bytes of an entry in LDS: four lanes' pieces
+typedef const uint8_t __attribute__((address_space(3))) *LvlLdsBytes;
+struct LvlRowReader {
+    LvlLdsBytes row;
+    bool &left; // a byte past the row was asked for
+    __device__ __forceinline__ int operator()(int i) const {
+        if (i < kLvlRowBytes) return row[i];
+        left = true;
+        return 0xFF;
+    }
+};
+struct LvlGlobalReader {
+    const uint8_t *pkt; // the entry's region; the rule asks below B only
+    __device__ __forceinline__ int operator()(int i) const { return pkt[i]; }
+};
+
+__global__ __launch_bounds__(kGatherBlock) void k_audio_level(AudioLevelArgs a) {
+    __shared__ uint4 rows[kGatherBlock / 64][4u * kLvlPerTrip]; // 1 KB per wave
+    const uint32_t lane = threadIdx.x & 63u, q = lane & 3u, e = lane >> 2;
+    uint4 *row = rows[threadIdx.x >> 6];
+    const uint32_t waves = gridDim.x * (kGatherBlock / 64);
+    uint32_t n_read = 0u, n_found = 0u, n_silent = 0u; // the wave's, the same in every lane
+    for (uint32_t j0 = kLvlPerTrip * (blockIdx.x * (kGatherBlock / 64) + (threadIdx.x >> 6)); j0 < a.n;
+         j0 += kLvlPerTrip * waves) {
+        const uint32_t j = j0 + e;
+        const bool in = j < a.n;
+        const uint32_t fl = in && a.flags ? a.flags[j] : 0u;
+        const int id = !in ? 0 : a.ext_ids ? (int)a.ext_ids[j] : a.ext_id;
+        const uint32_t at = in ? a.off[j] : 0u; // loaded beside len and cap: one round trip less in front of the bytes
+        const int B = in ? audio_level_wanted(fl, (int)a.len[j], (int)a.cap[j], id) : 0;
+        int level = kLvlNone;
+        if (__ballot(B != 0) != 0ull) { // the same for every lane of the wave
+            walk_sync();                // the previous trip's walks have read the rows
+            const uint8_t *pkt = nullptr;
+            if (B != 0) { // no pointer into the segment for any other entry
+                pkt = a.seg + at;
+                if ((int)(16u * q) < B) row[lane] = reinterpret_cast<const uint4 *>(pkt)[q];
+            }
+            walk_sync();
+            if (B != 0 && q == 0u) {
+                bool left = false;
+                const LvlRowReader rd{(LvlLdsBytes)(row + 4u * e), left};
+                level = audio_level_find(rd, B, id);
+                if (left) level = audio_level_find(LvlGlobalReader{pkt}, B, id);
+            }
+        }
+        if (in && q == 0u) {
+            a.level[j] = (int8_t)level;
+            a.flags_out[j] = audio_level_flags(fl, level);
+        }
+        n_read += (uint32_t)__popcll(__ballot(B != 0 && q == 0u));
+        n_found += (uint32_t)__popcll(__ballot(level >= 0));
+        n_silent += (uint32_t)__popcll(__ballot(level == kLvlMuted));
+    }
+    if (lane == 0u) { // one of kLvlStatReplicas rows, by wave: thousands of waves on one address queue up in the L2
+        unsigned long long *row_stats =
+            a.stats + kLvlStatStride * ((blockIdx.x * (kGatherBlock / 64) + (threadIdx.x >> 6)) % kLvlStatReplicas);
+        if (n_read) atomicAdd(row_stats + 0, (unsigned long long)n_read);
+        if (n_found) atomicAdd(row_stats + 1, (unsigned long long)n_found);
+        if (n_silent) atomicAdd(row_stats + 2, (unsigned long long)n_silent);
+    }
+}
+
+hipError_t launch_audio_level(const AudioLevelArgs &a, hipStream_t s) {
+    if (a.n == 0) return hipSuccess;
+    const uint32_t per_wg = kLvlPerTrip * (kGatherBlock / 64);
+    const uint32_t wgs = std::min<uint32_t>((a.n + per_wg - 1u) / per_wg, 2048u); // 32 waves per CU of 256
+    hipLaunchKernelGGL(k_audio_level, dim3(wgs), dim3(kGatherBlock), 0, s, a);
     return hipGetLastError();
 }
 

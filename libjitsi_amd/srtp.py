@@ -381,6 +381,81 @@ class SRTPEngine:
             cap.data_ptr(), None if flags is None else flags.data_ptr(), status.data_ptr(), n, sp)
         N.check(rc, self.h, "srtp_transform_device")
 
+    # -- receive with the ssrc-audio-level read on the device -------------------
+    def transform_device_lvl(self, tid, seg, off, length, cap, status, level, flags=None, ext_ids=None,
+                             ext_id: int = 0, n: Optional[int] = None, stream=None) -> None:
+        """srtp_transform_device_lvl: :meth:`transform_device` with
+        ``reverse=True`` and SsrcTransformEngine.reverseTransform
+        (SsrcTransformEngine.java:226-274) in front of it, on the device.
+        Entry i's ssrc-audio-level (RFC 6464, RawPacket.extractSsrcAudioLevel)
+        is written to ``level[i]`` (an int8 tensor of n elements: 0..127, or
+        -128 where the packet carries none) and an entry whose level is 127, a
+        muted source, is unprotected as if the caller had flagged it
+        ``N.PKT_FLAG_SILENCE``: authenticated, not deciphered.  ``ext_ids`` is
+        a uint8 tensor with one negotiated extension ID per entry, or None for
+        ``ext_id`` on every entry; an ID of 0 or above 127 reads nothing (pass
+        0 for SRTCP entries).  The level is reported whatever the packet's
+        SRTP status turns out to be; the reference, too, dispatches it before
+        authentication.  Async on ``stream`` like :meth:`transform_device`."""
+        if n is None:
+            n = off.numel()
+        if level.element_size() != 1 or level.numel() < n or not level.is_contiguous():
+            raise ValueError("level: a contiguous tensor of n 1-byte elements")
+        if ext_ids is not None and (ext_ids.element_size() != 1 or ext_ids.numel() < n or
+                                    not ext_ids.is_contiguous()):
+            raise ValueError("ext_ids: a contiguous tensor of n 1-byte elements")
+        if not 0 <= int(ext_id) <= 255:
+            raise ValueError("ext_id: a byte")
+        if np.isscalar(tid):
+            tids_p, tid0 = None, int(tid)
+        else:
+            tids_p, tid0 = tid.data_ptr(), -1
+        sp = getattr(stream, "cuda_stream", stream)
+        rc = N.lib().srtp_transform_device_lvl(
+            self.h, tids_p, tid0, seg.data_ptr(), off.data_ptr(), length.data_ptr(), cap.data_ptr(),
+            None if flags is None else flags.data_ptr(), None if ext_ids is None else ext_ids.data_ptr(),
+            int(ext_id), level.data_ptr(), status.data_ptr(), n, sp)
+        N.check(rc, self.h, "srtp_transform_device_lvl")
+
+    def transform_host_lvl(self, tid, seg: np.ndarray, off: np.ndarray, length: np.ndarray, cap: np.ndarray,
+                           flags=None, ext_ids=None, ext_id: int = 0):
+        """srtp_transform_host_lvl: :meth:`transform_host` with
+        ``reverse=True`` and the audio-level stage of
+        :meth:`transform_device_lvl` in front (SsrcTransformEngine.java:226-274).
+        ``ext_ids``: one uint8 ID per packet, or None for ``ext_id`` on every
+        packet.  Returns ``(status, level)``, ``level`` an int8 array."""
+        n = len(off)
+        assert seg.dtype == np.uint8 and seg.flags.c_contiguous
+        off = np.ascontiguousarray(off, np.uint32)
+        cap = np.ascontiguousarray(cap, np.uint32)
+        assert length.dtype == np.uint32 and length.flags.c_contiguous and len(length) == n
+        status = np.zeros(n, np.int32)
+        level = np.full(n, N.AUDIO_LEVEL_NONE, np.int8)
+        fl = None if flags is None else np.ascontiguousarray(flags, np.uint32)
+        ids = None if ext_ids is None else np.ascontiguousarray(ext_ids, np.uint8)
+        assert (fl is None or len(fl) == n) and (ids is None or len(ids) == n)
+        if not 0 <= int(ext_id) <= 255:
+            raise ValueError("ext_id: a byte")
+        if np.isscalar(tid):
+            tids_p, tid0 = None, int(tid)
+        else:
+            tids = np.ascontiguousarray(tid, np.int32)
+            assert len(tids) == n
+            tids_p, tid0 = tids.ctypes.data, -1
+        rc = N.lib().srtp_transform_host_lvl(
+            self.h, tids_p, tid0, seg.ctypes.data, seg.nbytes, off.ctypes.data, length.ctypes.data,
+            cap.ctypes.data, None if fl is None else fl.ctypes.data, None if ids is None else ids.ctypes.data,
+            int(ext_id), level.ctypes.data, status.ctypes.data, n)
+        N.check(rc, self.h, "srtp_transform_host_lvl")
+        return status, level
+
+    def audio_level_stats(self) -> dict:
+        """srtp_engine_audio_level_stats: the _lvl calls, the entries whose
+        bytes were read, the levels found and the entries flagged silent."""
+        st = N.AudioLevelStats()
+        N.check(N.lib().srtp_engine_audio_level_stats(self.h, C.byref(st)), self.h, "audio_level_stats")
+        return st.as_dict()
+
     # -- fan-out: one packet to many peers -----------------------------------
     def fanout_device(self, tid, src_seg, src_off, src_len, src_cap, src_idx, seg, off, length, cap, status,
                       src_status=None, flags=None, m: Optional[int] = None, n: Optional[int] = None,
@@ -1657,6 +1732,68 @@ def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None, payload=Fa
         o = int(off[j])
         out[k][i] = RawPacket(seg[o:o + int(ln[j])].tobytes(), 0, int(ln[j]), pkts[i].flags)
     return out
+
+
+def audio_level_job(pkt: bytes, length: int, cap: int, flags: int, ext_id: int):
+    """srtp_audio_level_job: the rule k_audio_level compiles
+    (libjitsi_amd/csrc/audio_level_job.h), on the host, over ``pkt``.  Returns
+    ``(level, flags_out)``."""
+    lv, fo = C.c_int8(), C.c_uint32()
+    buf = bytes(pkt)
+    N.check(N.lib().srtp_audio_level_job(buf, length, cap, flags, ext_id, C.byref(lv), C.byref(fo)), None,
+            "srtp_audio_level_job")
+    return lv.value, fo.value
+
+
+def reverse_transform_levels(pkts, transformer: _SRTPBase, ext_id: int):
+    """SsrcTransformEngine.reverseTransform (SsrcTransformEngine.java:226-274,
+    dropMutedAudioSourceInReverseTransform false) and the stream's SRTP
+    ``reverseTransform`` behind it (MediaStreamImpl.java:1037-1044) over the
+    list ``pkts`` of RawPacket, in one bundle on the GPU
+    (srtp_transform_host_lvl).  ``ext_id`` is the negotiated ssrc-audio-level
+    extension ID (a Java byte: 1..127 is on).  As ``reverseTransform`` does, it
+    works on the list in place: accepted packets are unprotected in their
+    buffers, dropped ones become None, and a packet from a muted source (level
+    127) gets ``FLAG_SILENCE`` in ``pkt.flags``, as the reference sets it, and
+    is authenticated but not deciphered.  Returns, per packet, the ``(ssrc,
+    127 - level, timestamp)`` tuple the reference hands to
+    CsrcAudioLevelDispatcher.addLevels, or None where the level is negative
+    (no such extension, or the packet was not read).  The level is reported
+    whatever the packet's later SRTP status: the reference also dispatches it
+    before authentication."""
+    levels = [None] * len(pkts)
+    if not len(pkts):
+        return levels
+    eng = transformer.engine
+    if not isinstance(eng, SRTPEngine):
+        raise ValueError("reverse_transform_levels: a transformer of an SRTPEngine")
+    seg, off, length, cap, flags = pack(pkts, transformer.packetPredicate, reverse=True)
+    status, level = eng.transform_host_lvl(transformer.tid, seg, off, length, cap, flags, None, int(ext_id) & 0xFF)
+    thrown = -1
+    for i, p in enumerate(pkts):
+        st = int(status[i])
+        if p is None or st == N.STATUS_SKIPPED:
+            continue
+        lv = int(level[i])
+        if lv >= 0:  # at least the fixed header is there (audio_level_wanted)
+            levels[i] = (p.readInt(8), 127 - lv, p.readInt(4))
+        if lv == N.AUDIO_LEVEL_MUTED:
+            p.flags |= N.PKT_FLAG_SILENCE
+        if st == N.STATUS_NOT_PROCESSED:
+            continue
+        if st == N.STATUS_OK:
+            o, nl = int(off[i]), int(length[i])
+            p.buffer[p.offset:p.offset + nl] = seg[o:o + nl].tobytes()
+            p.length = nl
+        elif st == N.STATUS_ERR_MALFORMED:
+            thrown = i if thrown < 0 else thrown
+        else:
+            pkts[i] = None
+    if thrown >= 0:
+        transformer._count_exception(True)
+        raise SRTPTransformException(
+            f"Failed to transform RawPacket(s)! (packet {thrown}: malformed for SRTP)")
+    return levels
 
 
 def transform_bundle(transformers: Sequence[Optional[_SRTPBase]], pkts, reverse: bool):
