@@ -517,6 +517,85 @@ int srtp_fanout_pay_job(int32_t src_idx, int32_t m, int32_t src_len, int32_t src
                         int32_t dst_cap, uint32_t flags, const srtp_fanout_payload *pay, int32_t q,
                         const uint32_t *words_in, uint32_t *words_out);
 
+/* Fan-out that strips or adds RED (RFC 2198) per destination: the one engine of
+ * the peer's send chain that moves the payload.  Chrome sends video as
+ * single-block RED; for a peer that did not negotiate it the reference runs
+ * REDFilterTransformEngine.transform (transform/REDFilterTransformEngine.java:
+ * 95-145), which takes the one-byte RED header out, and for a peer that did,
+ * when the source sent none, REDTransformEngine.transform (transform/
+ * REDTransformEngine.java:151-182, in the chain at MediaStreamImpl.java:993-996),
+ * which puts it in.  One 4-byte record per destination entry says which:
+ *   SRTP_RED_OFF    nothing (the reference's payload type -1, "disabled")
+ *   SRTP_RED_STRIP  a version-2 packet whose PT is red_pt, that is no RTCP by
+ *                   the predicate's test (byte 1 in 200..211, marker included)
+ *                   and whose header ends inside the packet loses the byte at
+ *                   getHeaderLength(); its 7 low bits become the PT.  Length - 1.
+ *   SRTP_RED_WRAP   a version-2 packet gets the byte (PT & 0x7F) at
+ *                   getHeaderLength() and red_pt as its PT.  Length + 1; where
+ *                   that exceeds cap[j] nothing is moved and the entry ends
+ *                   SRTP_STATUS_DROP_INVALID like a host-made copy.
+ * Where the reference throws -- a header that ends past the packet's bytes, an
+ * extension length word past them, a RED header with F set (at this revision a
+ * multi-block packet always throws, red_job.h says why) -- the packet is lost
+ * there and the entry is dropped here: nothing is copied, len[j] = 0, the entry
+ * ends SRTP_STATUS_SKIPPED and touches no context.  The step is asked for only
+ * when the entry is not skipped and the whole packet is there (min(src_len,
+ * src_cap, cap[j]) == src_len >= 12); otherwise the entry is the _pay call's.
+ * RED runs first: rewrite[j], pay[j] (its offsets in the new packet's
+ * coordinates) and stamp[j] apply to the packet RED left, with its new length,
+ * as ssrcRewritingEngine stands behind RED (MediaStreamImpl.java:998).  The
+ * source segment is never written.  red_job.h states the rule line by line. */
+#define SRTP_RED_OFF 0
+#define SRTP_RED_STRIP 1
+#define SRTP_RED_WRAP 2
+typedef struct { uint8_t mode, red_pt, reserved[2]; } srtp_fanout_red;
+/* red_out[j]: what became of entry j */
+#define SRTP_RED_UNTOUCHED 0
+#define SRTP_RED_STRIPPED 1
+#define SRTP_RED_WRAPPED 2
+#define SRTP_RED_DROPPED (-1)
+/* srtp_fanout_device_pay / srtp_fanout_host_pay with two more arguments after
+ * pay: red, n records (k_fanout_red), and red_out, n result codes (may be
+ * NULL).  red == NULL is the _pay call, exactly (red_out is then not written).
+ * With red set, rewrite, stamp and pay may each be NULL.  Device route: red is a
+ * device array, 4-byte aligned (else SRTP_EINVAL before any launch), red_out n
+ * bytes on the device; a record with mode > 2, red_pt > 127 or non-zero
+ * reserved bytes switches its entry's step off (result 0).  Host route: host
+ * arrays, the records staged like pay and red_out copied back with len and
+ * status; such a record is refused (SRTP_EINVAL, nothing launched). */
+int srtp_fanout_device_red(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
+                           const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status,
+                           uint32_t m, const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                           const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                           const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
+                           const srtp_fanout_payload *pay, const srtp_fanout_red *red, int8_t *red_out,
+                           int32_t *status, uint32_t n, void *stream);
+int srtp_fanout_host_red(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_bytes, const uint32_t *src_off,
+                         const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status,
+                         uint32_t m, const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                         size_t seg_bytes, const uint32_t *off, uint32_t *len, const uint32_t *cap,
+                         const uint32_t *flags, const srtp_fanout_rewrite *rewrite,
+                         const srtp_fanout_abs_send_time *stamp, const srtp_fanout_payload *pay,
+                         const srtp_fanout_red *red, int8_t *red_out, int32_t *status, uint32_t n);
+/* Counters of the _red calls with red set, cumulative since engine creation:
+ * the calls and the entries stripped, wrapped and dropped. */
+typedef struct {
+    uint64_t calls, stripped, wrapped, dropped;
+} srtp_fanout_red_stats;
+int srtp_engine_fanout_red_stats(srtp_engine *e, srtp_fanout_red_stats *out);
+/* The RED rule of one destination entry (host only; red_job.h, the text
+ * k_fanout_red compiles) over the caller's bytes: pkt[0 .. min(src_len, src_cap,
+ * dst_cap)) is the source packet as far as it is copied; the next seven
+ * arguments are srtp_fanout_job's.  result: SRTP_RED_UNTOUCHED / _STRIPPED /
+ * _WRAPPED / _DROPPED; h: getHeaderLength() where stripped or wrapped, else 0;
+ * len_out: the entry's length behind the step; shift: -1, +1 or 0. */
+typedef struct {
+    int32_t result, h, len_out, shift;
+} srtp_fanout_red_plan;
+int srtp_fanout_red_job(const uint8_t *pkt, int32_t src_idx, int32_t m, int32_t src_len, int32_t src_cap,
+                        int32_t src_status, int32_t dst_cap, uint32_t flags, const srtp_fanout_red *red,
+                        srtp_fanout_red_plan *out);
+
 /* The engine's own non-blocking stream, created with the engine so that each
  * engine gets a hardware queue of its own (streams created later may share
  * one, which serialises them): srtp_transform_host and the pipeline run their

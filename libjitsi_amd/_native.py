@@ -96,6 +96,7 @@ EXPORTED = [
     "srtp_fanout_device_pay", "srtp_fanout_host_pay", "srtp_fanout_pay_job",
     "srtp_transform_device_lvl", "srtp_transform_host_lvl", "srtp_engine_audio_level_stats",
     "srtp_audio_level_job",
+    "srtp_fanout_device_red", "srtp_fanout_host_red", "srtp_engine_fanout_red_stats", "srtp_fanout_red_job",
 ]
 STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 
@@ -103,7 +104,7 @@ STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 # Sources that decide what the crypto kernels execute: the key that ties
 # committed PMC counters (profiles/pmc_traffic.json) to the build they measured.
 KERNEL_SOURCES = ["srtp_kernels.hip", "aes_rounds_asm.inc", "srtp_kernels.h", "srtp_types.h", "engine.cpp",
-                  "gcm_job.h", "fanout_job.h", "bundle_plan.h", "audio_level_job.h"]
+                  "gcm_job.h", "fanout_job.h", "bundle_plan.h", "audio_level_job.h", "red_job.h"]
 
 
 def kernel_source_sha16() -> str:
@@ -230,6 +231,30 @@ class FanoutPayload(C.Structure):
 
 # numpy's view of an array of srtp_fanout_payload (fanout_host_pay)
 FANOUT_PAYLOAD_DTYPE = np.dtype([("at0", "<u2"), ("b0", "u1", (2,)), ("at1", "<u2"), ("b1", "u1", (2,))])
+
+
+class FanoutRed(C.Structure):
+    """srtp_fanout_red (include/srtp_mi355x.h): one destination entry's RED step"""
+    _fields_ = [("mode", C.c_uint8), ("red_pt", C.c_uint8), ("reserved", C.c_uint8 * 2)]
+
+
+# numpy's view of an array of srtp_fanout_red (fanout_host_red)
+FANOUT_RED_DTYPE = np.dtype([("mode", "u1"), ("red_pt", "u1"), ("reserved", "u1", (2,))])
+RED_OFF, RED_STRIP, RED_WRAP = 0, 1, 2  # srtp_fanout_red.mode
+RED_UNTOUCHED, RED_STRIPPED, RED_WRAPPED, RED_DROPPED = 0, 1, 2, -1  # red_out
+
+
+class FanoutRedPlan(C.Structure):
+    """srtp_fanout_red_plan (include/srtp_mi355x.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("result", "h", "len_out", "shift")]
+
+
+class FanoutRedStats(C.Structure):
+    """srtp_fanout_red_stats (include/srtp_mi355x.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "stripped", "wrapped", "dropped")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
 class AudioLevelStats(C.Structure):
@@ -403,6 +428,13 @@ def lib() -> C.CDLL:
                                        vp, vp, vp, vp, vp, vp, u32]
     L.srtp_fanout_pay_job.argtypes = [i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutPayload), i32,
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.srtp_fanout_device_red.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                         vp, vp, vp, u32, vp]
+    L.srtp_fanout_host_red.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, u32, vp, vp, i32, vp, C.c_size_t, vp, vp,
+                                       vp, vp, vp, vp, vp, vp, vp, vp, u32]
+    L.srtp_fanout_red_job.argtypes = [vp, i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutRed),
+                                      C.POINTER(FanoutRedPlan)]
+    L.srtp_engine_fanout_red_stats.argtypes = [vp, C.POINTER(FanoutRedStats)]
     L.srtp_engine_fanout_stats.argtypes = [vp, C.POINTER(FanoutStats)]
     L.srtp_fanout_job.argtypes = [i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutPlan)]
     L.srtp_transform_device_lvl.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, C.c_uint8, vp, vp, u32, vp]

@@ -21,6 +21,7 @@
 #include "../../include/srtp_mi355x.h"
 #include "audio_level_job.h"
 #include "fanout_job.h"
+#include "red_job.h"
 #include "gcm_job.h"
 #include "host_crypto.h"
 #include "srtp_kernels.h"
@@ -116,10 +117,14 @@ struct srtp_engine {
     unsigned long long *d_fan_skipped = nullptr;
     uint8_t *hs_seg = nullptr;
     size_t hs_seg_bytes = 0;
-    uint32_t hs_m = 0, hs_n = 0, hs_rw_n = 0, hs_ast_n = 0, hs_pay_n = 0;
+    uint32_t hs_m = 0, hs_n = 0, hs_rw_n = 0, hs_ast_n = 0, hs_pay_n = 0, hs_red_n = 0;
     srtp_fanout_rewrite *hs_rw = nullptr; // srtp_fanout_host_rw's records, staged like hs_idx
     srtp_fanout_abs_send_time *hs_ast = nullptr; // srtp_fanout_host_ast's records, likewise
     srtp_fanout_payload *hs_pay = nullptr; // srtp_fanout_host_pay's records, likewise
+    srtp_fanout_red *hs_red = nullptr; // srtp_fanout_host_red's records, likewise, and its result codes
+    int8_t *hs_red_out = nullptr;
+    unsigned long long *d_red_stats = nullptr; // k_fanout_red's rows of entries stripped, wrapped, dropped
+    uint64_t red_calls = 0;
     uint32_t *hs_off = nullptr, *hs_len = nullptr, *hs_cap = nullptr;
     int32_t *hs_status = nullptr, *hs_idx = nullptr;
     uint64_t fan_calls = 0, fan_sources = 0, fan_destinations = 0, fan_src_bytes = 0;
@@ -631,7 +636,7 @@ void srtp_engine_destroy(srtp_engine *e) {
                     e->d_far, e->e_min, e->ctl, e->d_count, e->d_counters, e->h_seg, e->h_off, e->h_len,
                     e->h_cap, e->h_flags, e->h_status, e->h_tids, e->fan_flags, e->d_fan_skipped, e->hs_seg,
                     e->hs_off, e->hs_len, e->hs_cap, e->hs_status, e->hs_idx, e->hs_rw, e->hs_ast, e->hs_pay,
-                    e->lvl_flags, e->d_lvl_stats, e->h_ext_ids, e->h_level};
+                    e->hs_red, e->hs_red_out, e->d_red_stats, e->lvl_flags, e->d_lvl_stats, e->h_ext_ids, e->h_level};
     for (void *p : ptrs) dfree(p);
     if (e->ev_last) (void)hipEventDestroy(e->ev_last);
     if (e->ev_dev) (void)hipEventDestroy(e->ev_dev);
@@ -1091,8 +1096,8 @@ static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t 
                          const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
                          const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
                          const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
-                         const srtp_fanout_payload *pay, int32_t *status, uint32_t n, hipStream_t s,
-                         bool dev_event) {
+                         const srtp_fanout_payload *pay, const srtp_fanout_red *red, int8_t *red_out,
+                         int32_t *status, uint32_t n, hipStream_t s, bool dev_event) {
     int rc = check_fanout(e, {src_seg, src_off, src_len, src_cap, src_idx, seg, off, len, cap, status}, m, n);
     if (rc == SRTP_OK && ((uintptr_t)rewrite & 15u)) // k_fanout_rw loads a record in one 16-byte piece
         rc = fail(e, SRTP_EINVAL, "rewrite must be 16-byte aligned");
@@ -1100,6 +1105,8 @@ static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t 
         rc = fail(e, SRTP_EINVAL, "stamp must be 8-byte aligned");
     if (rc == SRTP_OK && ((uintptr_t)pay & 7u)) // k_fanout_pay loads a record in one 8-byte piece
         rc = fail(e, SRTP_EINVAL, "pay must be 8-byte aligned");
+    if (rc == SRTP_OK && ((uintptr_t)red & 3u)) // k_fanout_red loads a record in one 4-byte piece
+        rc = fail(e, SRTP_EINVAL, "red must be 4-byte aligned");
     if (rc == SRTP_OK) rc = check_tid(e, tids != nullptr, tid);
     if (rc == SRTP_OK) rc = ensure_scratch(e, n);
     if (rc != SRTP_OK) return rc;
@@ -1113,7 +1120,13 @@ static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t 
     }
     if (!e->d_fan_skipped) {
         HIPCHK(e, dalloc(&e->d_fan_skipped, 1));
-        HIPCHK(e, hipMemset(e->d_fan_skipped, 0, sizeof(unsigned long long)));
+        // on `s`, in front of the kernel that adds to it: a memset on the null stream is not ordered with the
+        // engine's non-blocking streams, and could land after the first call's adds
+        HIPCHK(e, hipMemsetAsync(e->d_fan_skipped, 0, sizeof(unsigned long long), s));
+    }
+    if (red && !e->d_red_stats) {
+        HIPCHK(e, dalloc(&e->d_red_stats, kRedStatReplicas * kRedStatStride));
+        HIPCHK(e, hipMemsetAsync(e->d_red_stats, 0, kRedStatReplicas * kRedStatStride * sizeof(unsigned long long), s));
     }
     if (e->have_last && e->last_stream != s) HIPCHK(e, hipStreamWaitEvent(s, last_event(e), 0));
     FanoutArgs f{};
@@ -1123,13 +1136,31 @@ static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t 
     f.flags_out = e->fan_flags;
     f.skipped = e->d_fan_skipped;
     f.n = n;
-    HIPCHK(e, launch_fanout(f, s, rewrite, stamp, pay));
+    const FanRedArgs fr{reinterpret_cast<const uint32_t *>(red), red_out, e->d_red_stats};
+    HIPCHK(e, launch_fanout(f, s, rewrite, stamp, pay, red ? &fr : nullptr));
     rc = transform_locked(e, 0, tids, tid, seg, off, len, cap, e->fan_flags, status, n, s, -1, dev_event);
     if (rc != SRTP_OK) return rc;
     e->fan_calls++;
     e->fan_sources += m;
     e->fan_destinations += n;
+    if (red) e->red_calls++;
     return SRTP_OK;
+}
+
+int srtp_fanout_device_red(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
+                           const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status, uint32_t m,
+                           const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                           const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                           const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
+                           const srtp_fanout_payload *pay, const srtp_fanout_red *red, int8_t *red_out,
+                           int32_t *status, uint32_t n, void *stream) {
+    if (!e) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (n == 0) return SRTP_OK;
+    GUARD(e);
+    return fanout_locked(e, src_seg, src_off, src_len, src_cap, src_status, m, src_idx, tids, tid, seg, off, len,
+                         cap, flags, rewrite, stamp, pay, red, red ? red_out : nullptr, status, n,
+                         (hipStream_t)stream, true);
 }
 
 int srtp_fanout_device_pay(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
@@ -1138,12 +1169,8 @@ int srtp_fanout_device_pay(srtp_engine *e, const uint8_t *src_seg, const uint32_
                            const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
                            const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
                            const srtp_fanout_payload *pay, int32_t *status, uint32_t n, void *stream) {
-    if (!e) return SRTP_EINVAL;
-    std::lock_guard<std::mutex> g(e->mu);
-    if (n == 0) return SRTP_OK;
-    GUARD(e);
-    return fanout_locked(e, src_seg, src_off, src_len, src_cap, src_status, m, src_idx, tids, tid, seg, off, len,
-                         cap, flags, rewrite, stamp, pay, status, n, (hipStream_t)stream, true);
+    return srtp_fanout_device_red(e, src_seg, src_off, src_len, src_cap, src_status, m, src_idx, tids, tid, seg, off,
+                                  len, cap, flags, rewrite, stamp, pay, nullptr, nullptr, status, n, stream);
 }
 
 int srtp_fanout_device_ast(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
@@ -1207,6 +1234,18 @@ int srtp_fanout_host_pay(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
                          const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
                          const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
                          const srtp_fanout_payload *pay, int32_t *status, uint32_t n) {
+    return srtp_fanout_host_red(e, src_seg, src_seg_bytes, src_off, src_len, src_cap, src_status, m, src_idx, tids,
+                                tid, seg, seg_bytes, off, len, cap, flags, rewrite, stamp, pay, nullptr, nullptr,
+                                status, n);
+}
+
+int srtp_fanout_host_red(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_bytes, const uint32_t *src_off,
+                         const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status, uint32_t m,
+                         const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg, size_t seg_bytes,
+                         const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                         const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
+                         const srtp_fanout_payload *pay, const srtp_fanout_red *red, int8_t *red_out,
+                         int32_t *status, uint32_t n) {
     if (!e) return SRTP_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     if (n == 0) return SRTP_OK;
@@ -1218,6 +1257,9 @@ int srtp_fanout_host_pay(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
         if (src_idx[j] < 0 || (uint32_t)src_idx[j] >= m) return fail(e, SRTP_EINVAL, "src_idx[j] names no source");
     for (uint32_t j = 0; rewrite && j < n; j++)
         if (rewrite[j].mask & ~kFanRewriteAll) return fail(e, SRTP_EINVAL, "rewrite[j].mask has a bit above 0xF");
+    for (uint32_t j = 0; red && j < n; j++)
+        if (red[j].mode > SRTP_RED_WRAP || red[j].red_pt > 127 || red[j].reserved[0] || red[j].reserved[1])
+            return fail(e, SRTP_EINVAL, "red[j] has a field out of range");
     rc = check_tid(e, tids != nullptr, tid);
     if (rc != SRTP_OK) return rc;
     GUARD(e);
@@ -1226,7 +1268,8 @@ int srtp_fanout_host_pay(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
     if (rc != SRTP_OK) return rc;
     const size_t need = (src_seg_bytes + 15) & ~(size_t)15;
     if ((need > e->hs_seg_bytes || m > e->hs_m || n > e->hs_n || (rewrite && n > e->hs_rw_n) ||
-         (stamp && n > e->hs_ast_n) || (pay && n > e->hs_pay_n)) &&
+         (stamp && n > e->hs_ast_n) || (pay && n > e->hs_pay_n) ||
+         (red && n > e->hs_red_n)) &&
         e->have_last) {
         rc = quiesce(e); // the source staging may still be read by an enqueued fan-out
         if (rc != SRTP_OK) return rc;
@@ -1237,6 +1280,7 @@ int srtp_fanout_host_pay(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
     if (rc == SRTP_OK && rewrite) rc = grow_staging(e, &e->hs_rw_n, n, &e->hs_rw);
     if (rc == SRTP_OK && stamp) rc = grow_staging(e, &e->hs_ast_n, n, &e->hs_ast);
     if (rc == SRTP_OK && pay) rc = grow_staging(e, &e->hs_pay_n, n, &e->hs_pay);
+    if (rc == SRTP_OK && red) rc = grow_staging(e, &e->hs_red_n, n, &e->hs_red, &e->hs_red_out);
     if (rc != SRTP_OK) return rc;
     // only the source segment and the small arrays cross to the device
     HIPCHK(e, hipMemcpyAsync(e->hs_seg, src_seg, src_seg_bytes, hipMemcpyHostToDevice, s));
@@ -1248,6 +1292,7 @@ int srtp_fanout_host_pay(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
     if (rewrite) HIPCHK(e, hipMemcpyAsync(e->hs_rw, rewrite, n * sizeof *rewrite, hipMemcpyHostToDevice, s));
     if (stamp) HIPCHK(e, hipMemcpyAsync(e->hs_ast, stamp, n * sizeof *stamp, hipMemcpyHostToDevice, s));
     if (pay) HIPCHK(e, hipMemcpyAsync(e->hs_pay, pay, n * sizeof *pay, hipMemcpyHostToDevice, s));
+    if (red) HIPCHK(e, hipMemcpyAsync(e->hs_red, red, n * sizeof *red, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(e->h_off, off, n * 4ull, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(e->h_cap, cap, n * 4ull, hipMemcpyHostToDevice, s));
     if (flags) HIPCHK(e, hipMemcpyAsync(e->h_flags, flags, n * 4ull, hipMemcpyHostToDevice, s));
@@ -1255,13 +1300,34 @@ int srtp_fanout_host_pay(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
     rc = fanout_locked(e, e->hs_seg, e->hs_off, e->hs_len, e->hs_cap, src_status ? e->hs_status : nullptr, m,
                        e->hs_idx, tids ? e->h_tids : nullptr, tid, e->h_seg, e->h_off, e->h_len, e->h_cap,
                        flags ? e->h_flags : nullptr, rewrite ? e->hs_rw : nullptr, stamp ? e->hs_ast : nullptr,
-                       pay ? e->hs_pay : nullptr, e->h_status, n, s, false);
+                       pay ? e->hs_pay : nullptr, red ? e->hs_red : nullptr, red ? e->hs_red_out : nullptr,
+                       e->h_status, n, s, false);
     if (rc != SRTP_OK) return rc;
     e->fan_src_bytes += src_seg_bytes;
     HIPCHK(e, hipMemcpyAsync(seg, e->h_seg, seg_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipMemcpyAsync(len, e->h_len, n * 4ull, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipMemcpyAsync(status, e->h_status, n * 4ull, hipMemcpyDeviceToHost, s));
+    if (red && red_out) HIPCHK(e, hipMemcpyAsync(red_out, e->hs_red_out, n, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
+    return SRTP_OK;
+}
+
+int srtp_engine_fanout_red_stats(srtp_engine *e, srtp_fanout_red_stats *out) {
+    if (!e || !out) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    memset(out, 0, sizeof *out);
+    out->calls = e->red_calls;
+    if (!e->d_red_stats) return SRTP_OK; // no _red call yet
+    GUARD(e);
+    int rc = quiesce(e);
+    if (rc != SRTP_OK) return rc;
+    unsigned long long st[kRedStatReplicas * kRedStatStride];
+    HIPCHK(e, hipMemcpy(st, e->d_red_stats, sizeof st, hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < kRedStatReplicas; r++) { // a row per group of waves (k_fanout_red)
+        out->stripped += st[r * kRedStatStride + 0];
+        out->wrapped += st[r * kRedStatStride + 1];
+        out->dropped += st[r * kRedStatStride + 2];
+    }
     return SRTP_OK;
 }
 
@@ -1359,6 +1425,32 @@ int srtp_fanout_pay_job(int32_t src_idx, int32_t m, int32_t src_len, int32_t src
     return SRTP_OK;
 }
 
+int srtp_fanout_red_job(const uint8_t *pkt, int32_t src_idx, int32_t m, int32_t src_len, int32_t src_cap,
+                        int32_t src_status, int32_t dst_cap, uint32_t flags, const srtp_fanout_red *red,
+                        srtp_fanout_red_plan *out) {
+    if (!red || !out) return SRTP_EINVAL;
+    static_assert(sizeof(srtp_fanout_red) == 4 && offsetof(srtp_fanout_red, red_pt) == 1 &&
+                      offsetof(srtp_fanout_red, reserved) == 2,
+                  "k_fanout_red loads a record as one 32-bit word");
+    static_assert(SRTP_RED_OFF == kRedOff && SRTP_RED_STRIP == kRedStrip && SRTP_RED_WRAP == kRedWrap &&
+                      SRTP_RED_UNTOUCHED == kRedUntouched && SRTP_RED_STRIPPED == kRedStripped &&
+                      SRTP_RED_WRAPPED == kRedWrapped && SRTP_RED_DROPPED == kRedDropped,
+                  "red_job.h restates these constants");
+    const FanoutJob j = fanout_job(src_idx, m, src_len, src_cap, src_status, dst_cap, flags);
+    const int c = red_wanted(j, src_len, src_cap, dst_cap, red->mode, red->red_pt,
+                             (uint32_t)red->reserved[0] | ((uint32_t)red->reserved[1] << 8));
+    RedPlan p = red_plan_of(kRedUntouched, 0, 0, 0, 0, 0);
+    if (c) {
+        if (!pkt) return SRTP_EINVAL;
+        p = red_rule(HostBytes{pkt, c}, c, red->mode, red->red_pt);
+    }
+    out->result = p.result;
+    out->h = p.h;
+    out->len_out = red_job(j, p, dst_cap).len_out;
+    out->shift = p.shift;
+    return SRTP_OK;
+}
+
 // ------------------------------------------------------------- audio levels
 // k_audio_level in front of the unprotect chain, both on `s`.  The flags words
 // the chain reads are the engine's (lvl_flags), so the stage waits, like a
@@ -1381,7 +1473,7 @@ static int lvl_locked(srtp_engine *e, const int32_t *tids, int32_t tid, uint8_t 
     }
     if (!e->d_lvl_stats) {
         HIPCHK(e, dalloc(&e->d_lvl_stats, kLvlStatReplicas * kLvlStatStride));
-        HIPCHK(e, hipMemset(e->d_lvl_stats, 0, kLvlStatReplicas * kLvlStatStride * sizeof(unsigned long long)));
+        HIPCHK(e, hipMemsetAsync(e->d_lvl_stats, 0, kLvlStatReplicas * kLvlStatStride * sizeof(unsigned long long), s));
     }
     if (e->have_last && e->last_stream != s) HIPCHK(e, hipStreamWaitEvent(s, last_event(e), 0));
     AudioLevelArgs a{};

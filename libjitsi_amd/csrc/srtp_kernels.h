@@ -185,9 +185,23 @@ struct FanoutArgs {
 // (srtp_fanout_payload), 8-byte aligned, in device memory: entry j's copy gets
 // pay[j]'s two patches where fanout_pay_on says so (k_fanout_pay, with or
 // without rewrite and stamp; picked only when pay is not null).  The two last
-// instances are the ones that use LDS.
+// instances are the ones that use LDS.  red: null, or what k_fanout_red gets
+// besides: n 4-byte records (srtp_fanout_red as one word: mode | red_pt << 8 |
+// reserved << 16), 4-byte aligned, in device memory -- entry j's copy has its
+// RED header taken out or put in where red_rule (red_job.h) says so, in front
+// of its other records; red_out, null or n result codes; stats,
+// kRedStatReplicas rows of kRedStatStride words (64 bytes): a wave adds its
+// entries stripped, wrapped and dropped to words 0..2 of one row, and the host
+// sums the rows.  k_fanout_red is picked only when red is not null; rewrite,
+// stamp and pay may then each be null.
+constexpr uint32_t kRedStatReplicas = 64, kRedStatStride = 8;
+struct FanRedArgs {
+    const uint32_t *red;
+    int8_t *red_out;
+    unsigned long long *stats; // [kRedStatReplicas][kRedStatStride]
+};
 hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s, const void *rewrite = nullptr,
-                         const void *stamp = nullptr, const void *pay = nullptr);
+                         const void *stamp = nullptr, const void *pay = nullptr, const FanRedArgs *red = nullptr);
 // srtp_transform_device_lvl: in front of the unprotect chain, entry j's
 // ssrc-audio-level is read and its flags word made (k_audio_level, the rule in
 // audio_level_job.h): level[j] = the level (0..127) or -128, flags_out[j] =

@@ -66,6 +66,7 @@
 #include "audio_level_job.h"
 #include "fanout_job.h"
 #include "gcm_job.h"
+#include "red_job.h"
 #include "srtp_kernels.h"
 
 namespace srtp {
@@ -7464,11 +7465,248 @@ __global__ __launch_bounds__(kGatherBlock) void k_fanout_pay(FanoutArgs f, const
     }
 }
 
+// The RED instance (k_fanout_red, srtp_fanout_*_red): entry j carries the
+// record red[j] (mode | red_pt << 8 | reserved << 16, red_job.h) and, where
+// given, rewrite[j], pay[j] and stamp[j] as above.  RED runs first: it moves the
+// payload by one byte and changes the length, and every other record of the
+// entry then applies to the packet RED left.
+//
+// In front of the copy loop red_wanted says from the job and the entry's own
+// record whether any byte is read.  The wave parks each such entry's first 256
+// source bytes in its LDS row, as k_fanout_ast does (the row is shared with the
+// abs-send-time walk: one staging for both), and lanes 0 and 1 run red_rule
+// over entry a's and entry b's half: bytes 0 and 1, the extension length word
+// (at most bytes 74 and 75: inside the row) and byte h, which past the row is
+// one global byte load below c.  The reader holds an LDS pointer and a global
+// pointer of their own address spaces and never joins them (k_fanout_ast's and
+// k_audio_level's lesson).  The plans are broadcast; red_job gives the job the
+// later records are asked with, and the walk reads through red_byte and
+// fanout_pay_byte.
+//
+// The copy loop runs over the destination's pieces.  Piece q of an entry with
+// shift d takes one aligned 16-byte load, source piece q, and one aligned
+// 4-byte load, the source word beside it that the shift pulls its one byte
+// from (word 4 q - 1 for wrap, 4 q + 4 for strip), funnelled by red_piece:
+// plain shifts and selects.  Every load of a trip is issued before its stores;
+// the funnelled piece goes through fan_patched, fan_paid and fan_stamped.
+//
+// Bounds.  With ws = the source's pieces (fanout_job: 16 ws = c rounded up, at
+// most src_cap rounded up to 16) and wd = the destination's (red_job: 16 wd =
+// the new length rounded up, and only when the new length is at most dst_cap,
+// so at most dst_cap rounded up to 16):
+//   loads   piece min(q, ws - 1) and word clamp(4 q -+ .., 0, 4 ws - 1): below
+//           16 ws.  Wrap with c = 16 k has wd = ws + 1: its last piece's loads
+//           are the clamped ones, and what they feed lies at or past the new
+//           length but for the top byte of word 4 ws - 1, source byte c - 1.
+//   stores  piece q < wd only.
+//   the source segment is never written.
+//   an entry without destination pieces -- skipped, dropped, a wrap that does
+//   not fit -- forms no destination pointer: it borrows its partner's with
+//   every access predicated off.  An entry whose header is read has source
+//   bytes (c >= 12).
+// The counters go to one of kRedStatReplicas rows by wave, as k_audio_level's.
+typedef const uint8_t __attribute__((address_space(3))) *FanLdsBytes;
+struct FanRedReader { // the source's bytes: the row below `staged`, the region past it
+    FanLdsBytes row;
+    const uint8_t *src;
+    int staged;
+    __device__ __forceinline__ int operator()(int i) const {
+        if (i < staged) return row[i];
+        return src[i];
+    }
+};
+struct FanRedWalkReader { // the walk's bytes: the packet RED left, behind the entry's two patches
+    FanRedReader rd;
+    RedPlan r;
+    FanPay p;
+    __device__ __forceinline__ int operator()(int i) const {
+        return fanout_pay_byte(fanout_pay_byte(red_byte(rd, i, r), i, p.at0, p.v00, p.v01, p.c), i, p.at1, p.v10,
+                               p.v11, p.c);
+    }
+};
+// rec: the entry's own record as loaded
+__device__ __forceinline__ int fan_red_wanted(const FanEntry &e, uint32_t rec) {
+    return red_wanted(e.job, e.src_len, e.src_cap, e.dst_cap, rec & 0xFFu, (rec >> 8) & 0xFFu, rec >> 16);
+}
+// The plan from its two broadcast words (result | pt << 8 | ins << 16, h) and the entry's c.
+__device__ __forceinline__ RedPlan fan_red_plan(int w, int h, int c) {
+    const int result = (int)(int8_t)(w & 0xFF);
+    const int shift = result == kRedStripped ? -1 : result == kRedWrapped ? 1 : 0;
+    return red_plan_of(result, h, result == kRedDropped ? 0 : c + shift, shift, (w >> 16) & 0xFF, (w >> 8) & 0x7F);
+}
+// The entry as the later records see it.
+__device__ __forceinline__ FanEntry fan_red_entry(const FanEntry &e, const RedPlan &p) {
+    FanEntry o = e;
+    o.job = red_job(e.job, p, e.dst_cap);
+    o.src_len = red_src_len(p, e.src_len);
+    o.src_cap = red_src_cap(p, e.src_cap);
+    return o;
+}
+// Destination piece q from source piece A and the word beside it.
+__device__ __forceinline__ uint4 fan_red(const uint4 &A, uint32_t nb, uint32_t q, const RedPlan &p) {
+    const FanoutPiece o =
+        red_piece(FanoutPiece{A.x, A.y, A.z, A.w}, nb, (int)q, p.shift, p.h, (uint32_t)p.ins, (uint32_t)p.pt);
+    return uint4{o.w0, o.w1, o.w2, o.w3};
+}
+
+__global__ __launch_bounds__(kGatherBlock) void k_fanout_red(FanoutArgs f, const uint4 *rewrite, const uint2 *stamp,
+                                                             const uint2 *pay, FanRedArgs r) {
+    __shared__ uint4 rows[kGatherBlock / 64][2u * kFanAstLanes];
+    const uint32_t lane = threadIdx.x & 63u;
+    uint4 *row = rows[threadIdx.x >> 6];
+    const uint32_t waves = gridDim.x * (kGatherBlock / 64);
+    uint32_t n_strip = 0u, n_wrap = 0u, n_drop = 0u; // the wave's, the same in every lane
+    for (uint32_t j = 2u * (blockIdx.x * (kGatherBlock / 64) + (threadIdx.x >> 6)); j < f.n; j += 2u * waves) {
+        const bool two = j + 1u < f.n;
+        const uint32_t j1 = two ? j + 1u : j;
+        const FanEntry ea = fan_entry(f, j), eb = fan_entry(f, j1);
+        const uint32_t oa = f.off[j], ob = f.off[j1]; // values only: a pointer is formed below, where there are bytes
+        const uint32_t ka = r.red[j], kb = r.red[j1];
+        // the source's pieces; a second entry that is not there has none
+        const uint32_t wa = (uint32_t)ea.job.copy_bytes / 16u, wb = two ? (uint32_t)eb.job.copy_bytes / 16u : 0u;
+        RedPlan pla = red_plan_of(kRedUntouched, 0, 0, 0, 0, 0), plb = pla;
+        FanEntry na = ea, nb = eb; // the entries behind RED
+        uint4 ra = {}, rb = {};
+        uint2 sa = {}, sb = {};
+        bool pa = false, pb = false;
+        FanPay ya = fan_pay(uint2{}, 0), yb = ya;
+        int ata = -1, atb = -1;
+        const uint4 *fa = nullptr, *fb = nullptr;
+        if ((wa | wb) != 0u) { // else no work: no pointer is formed
+            fa = reinterpret_cast<const uint4 *>(f.src_seg + (wa ? ea.src_at : eb.src_at));
+            fb = reinterpret_cast<const uint4 *>(f.src_seg + (wb ? eb.src_at : ea.src_at));
+            if (stamp) {
+                sa = stamp[j];
+                sb = stamp[j1];
+            }
+            // an entry without bytes, or a second entry that is not there, is asked nothing
+            const int qa = wa ? fan_red_wanted(ea, ka) : 0, qb = wb ? fan_red_wanted(eb, kb) : 0;
+            const int ca0 = stamp && wa ? fan_ast_wanted(ea, sa) : 0, cb0 = stamp && wb ? fan_ast_wanted(eb, sb) : 0;
+            const bool staged = (qa | qb | ca0 | cb0) != 0; // the same for every lane of the wave
+            const FanRedReader rda{(FanLdsBytes)row, reinterpret_cast<const uint8_t *>(fa),
+                                   (int)min(kFanAstPrefix, 16u * wa)};
+            const FanRedReader rdb{(FanLdsBytes)(row + kFanAstLanes), reinterpret_cast<const uint8_t *>(fb),
+                                   (int)min(kFanAstPrefix, 16u * wb)};
+            if (staged) {
+                walk_sync(); // the previous pair's walk has read the row
+                const uint32_t piece = lane & (kFanAstLanes - 1u);
+                if (lane < kFanAstLanes) {
+                    if ((qa | ca0) && piece < wa) row[lane] = fa[piece];
+                } else if (lane < 2u * kFanAstLanes) {
+                    if ((qb | cb0) && piece < wb) row[lane] = fb[piece];
+                }
+                walk_sync();
+            }
+            if ((qa | qb) != 0) { // the same for every lane of the wave
+                int w = 0, h = 0;
+                if (lane == 0u && qa) {
+                    const RedPlan p = red_rule(rda, qa, (int)(ka & 0xFFu), (int)((ka >> 8) & 0xFFu));
+                    w = (p.result & 0xFF) | (p.pt << 8) | (p.ins << 16);
+                    h = p.h;
+                } else if (lane == 1u && qb) {
+                    const RedPlan p = red_rule(rdb, qb, (int)(kb & 0xFFu), (int)((kb >> 8) & 0xFFu));
+                    w = (p.result & 0xFF) | (p.pt << 8) | (p.ins << 16);
+                    h = p.h;
+                }
+                pla = fan_red_plan(__builtin_amdgcn_readlane(w, 0), __builtin_amdgcn_readlane(h, 0), qa);
+                plb = fan_red_plan(__builtin_amdgcn_readlane(w, 1), __builtin_amdgcn_readlane(h, 1), qb);
+                na = fan_red_entry(ea, pla);
+                nb = fan_red_entry(eb, plb);
+            }
+            // each entry's own records, by its own index, asked with the entry RED left
+            if (rewrite) {
+                ra = rewrite[j];
+                rb = rewrite[j1];
+                pa = fan_patches(na, ra);
+                pb = two && fan_patches(nb, rb);
+            }
+            if (pay) {
+                ya = fan_pay(pay[j], wa ? fanout_pay_bound(na.job, na.src_len, na.src_cap, na.dst_cap) : 0);
+                yb = fan_pay(pay[j1], wb ? fanout_pay_bound(nb.job, nb.src_len, nb.src_cap, nb.dst_cap) : 0);
+            }
+            if (stamp) {
+                // wanted behind RED implies staged: the row is there where RED was asked for, and where it
+                // was not, the entry is what it was
+                const int ca = wa ? fan_ast_wanted(na, sa) : 0, cb = wb ? fan_ast_wanted(nb, sb) : 0;
+                if (staged && (ca | cb) != 0) { // the same for every lane of the wave
+                    int at = -1;
+                    if (lane == 0u && ca) {
+                        const FanRedWalkReader rd{rda, pla, ya};
+                        at = fanout_ast_find(rd, na.job, na.src_len, na.src_cap, na.dst_cap, (sa.y >> 8) & 0xFFu,
+                                             sa.y & 0xFFu);
+                    } else if (lane == 1u && cb) {
+                        const FanRedWalkReader rd{rdb, plb, yb};
+                        at = fanout_ast_find(rd, nb.job, nb.src_len, nb.src_cap, nb.dst_cap, (sb.y >> 8) & 0xFFu,
+                                             sb.y & 0xFFu);
+                    }
+                    ata = __builtin_amdgcn_readlane(at, 0);
+                    atb = __builtin_amdgcn_readlane(at, 1);
+                }
+            }
+        }
+        if (lane == 0u) {
+            f.len[j] = (uint32_t)na.job.len_out;
+            f.flags_out[j] = na.job.flags_out;
+            if (r.red_out) r.red_out[j] = (int8_t)pla.result;
+            if (two) {
+                f.len[j + 1u] = (uint32_t)nb.job.len_out;
+                f.flags_out[j + 1u] = nb.job.flags_out;
+                if (r.red_out) r.red_out[j + 1u] = (int8_t)plb.result;
+            }
+            const unsigned long long sk = (unsigned long long)(ea.job.by_source + (two ? eb.job.by_source : 0));
+            if (sk) atomicAdd(f.skipped, sk);
+        }
+        n_strip += (uint32_t)(pla.result == kRedStripped) + (uint32_t)(plb.result == kRedStripped);
+        n_wrap += (uint32_t)(pla.result == kRedWrapped) + (uint32_t)(plb.result == kRedWrapped);
+        n_drop += (uint32_t)(pla.result == kRedDropped) + (uint32_t)(plb.result == kRedDropped);
+        // the destination's pieces; wda > 0 implies wa > 0 (red_job hands out bytes only where fanout_job did)
+        const uint32_t wda = (uint32_t)na.job.copy_bytes / 16u, wdb = two ? (uint32_t)nb.job.copy_bytes / 16u : 0u;
+        if ((wda | wdb) == 0u) continue; // nothing to store: no destination pointer is formed
+        uint4 *ta = reinterpret_cast<uint4 *>(f.seg + (wda ? oa : ob));
+        uint4 *tb = reinterpret_cast<uint4 *>(f.seg + (wdb ? ob : oa));
+        const uint32_t *ga = reinterpret_cast<const uint32_t *>(fa), *gb = reinterpret_cast<const uint32_t *>(fb);
+        const bool da = pla.shift != 0, db = plb.shift != 0;
+        for (uint32_t o = lane; o < max(wda, wdb); o += 128u) {
+            const bool a0 = o < wda, a1 = o + 64u < wda, b0 = o < wdb, b1 = o + 64u < wdb;
+            uint4 x0, x1, y0, y1;
+            uint32_t u0 = 0u, u1 = 0u, v0 = 0u, v1 = 0u;
+            if (a0) x0 = fa[red_src_piece((int)o, (int)wa)];
+            if (a1) x1 = fa[red_src_piece((int)(o + 64u), (int)wa)];
+            if (b0) y0 = fb[red_src_piece((int)o, (int)wb)];
+            if (b1) y1 = fb[red_src_piece((int)(o + 64u), (int)wb)];
+            if (a0 && da) u0 = ga[red_src_word((int)o, pla.shift, (int)wa)];
+            if (a1 && da) u1 = ga[red_src_word((int)(o + 64u), pla.shift, (int)wa)];
+            if (b0 && db) v0 = gb[red_src_word((int)o, plb.shift, (int)wb)];
+            if (b1 && db) v1 = gb[red_src_word((int)(o + 64u), plb.shift, (int)wb)];
+            // the trip's one wait, said here for every lane (k_fanout_pay says why)
+            __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0), expcnt and lgkmcnt left alone
+            if (a0)
+                ta[o] = fan_stamped(fan_paid(fan_patched(fan_red(x0, u0, o, pla), ra, pa && o == 0u), o, ya), o, ata,
+                                    sa.x);
+            if (a1) ta[o + 64u] = fan_stamped(fan_paid(fan_red(x1, u1, o + 64u, pla), o + 64u, ya), o + 64u, ata, sa.x);
+            if (b0)
+                tb[o] = fan_stamped(fan_paid(fan_patched(fan_red(y0, v0, o, plb), rb, pb && o == 0u), o, yb), o, atb,
+                                    sb.x);
+            if (b1) tb[o + 64u] = fan_stamped(fan_paid(fan_red(y1, v1, o + 64u, plb), o + 64u, yb), o + 64u, atb, sb.x);
+        }
+    }
+    if (lane == 0u) { // one of kRedStatReplicas rows, by wave: many waves on one address queue up in the L2
+        unsigned long long *row_stats =
+            r.stats + kRedStatStride * ((blockIdx.x * (kGatherBlock / 64) + (threadIdx.x >> 6)) % kRedStatReplicas);
+        if (n_strip) atomicAdd(row_stats + 0, (unsigned long long)n_strip);
+        if (n_wrap) atomicAdd(row_stats + 1, (unsigned long long)n_wrap);
+        if (n_drop) atomicAdd(row_stats + 2, (unsigned long long)n_drop);
+    }
+}
+
 hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s, const void *rewrite, const void *stamp,
-                         const void *pay) {
+                         const void *pay, const FanRedArgs *red) {
     if (f.n == 0) return hipSuccess;
     const uint32_t wgs = std::min<uint32_t>((f.n + 7u) / 8u, 4096u); // two entries per wave
-    if (pay)
+    if (red)
+        hipLaunchKernelGGL(k_fanout_red, dim3(wgs), dim3(kGatherBlock), 0, s, f, static_cast<const uint4 *>(rewrite),
+                           static_cast<const uint2 *>(stamp), static_cast<const uint2 *>(pay), *red);
+    else if (pay)
         hipLaunchKernelGGL(k_fanout_pay, dim3(wgs), dim3(kGatherBlock), 0, s, f, static_cast<const uint4 *>(rewrite),
                            static_cast<const uint2 *>(stamp), static_cast<const uint2 *>(pay));
     else if (stamp)

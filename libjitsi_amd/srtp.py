@@ -578,6 +578,53 @@ class SRTPEngine:
             status.data_ptr(), n, sp)
         N.check(rc, self.h, "srtp_fanout_device_pay")
 
+    def fanout_device_red(self, tid, src_seg, src_off, src_len, src_cap, src_idx, seg, off, length, cap, status,
+                          rewrite, stamp, pay, red, red_out, src_status=None, flags=None, m: Optional[int] = None,
+                          n: Optional[int] = None, stream=None) -> None:
+        """srtp_fanout_device_red: :meth:`fanout_device_pay` with one RED
+        (RFC 2198) record per destination entry.  ``red`` is a tensor on this
+        engine's GPU that holds n x 4 bytes, 4-byte aligned (n records of
+        ``N.FANOUT_RED_DTYPE``: mode, red_pt, reserved), or None for
+        :meth:`fanout_device_pay` exactly; ``rewrite``, ``stamp`` and ``pay``
+        may each be None either way.  ``N.RED_STRIP`` takes the one-byte RED
+        header of a single-block packet whose PT is ``red_pt`` out of entry j's
+        copy (REDFilterTransformEngine.java:95-145: length - 1), ``N.RED_WRAP``
+        puts one in and makes ``red_pt`` the PT (REDTransformEngine.java:151-182:
+        length + 1), ``N.RED_OFF`` leaves the entry to the other records.
+        Where the reference throws the entry is dropped: it ends
+        ``STATUS_SKIPPED``.  ``red_out`` (None, or an int8 tensor of n
+        elements) gets what became of each entry: ``N.RED_UNTOUCHED``,
+        ``N.RED_STRIPPED``, ``N.RED_WRAPPED`` or ``N.RED_DROPPED``.  RED runs
+        first; the other records apply to the packet it left."""
+        if m is None:
+            m = src_off.numel()
+        if n is None:
+            n = off.numel()
+        if rewrite is not None and rewrite.numel() * rewrite.element_size() < 16 * n:
+            raise ValueError("fanout_device_red: rewrite holds fewer than n records")
+        if stamp is not None and stamp.numel() * stamp.element_size() < 8 * n:
+            raise ValueError("fanout_device_red: stamp holds fewer than n records")
+        if pay is not None and pay.numel() * pay.element_size() < 8 * n:
+            raise ValueError("fanout_device_red: pay holds fewer than n records")
+        if red is not None and red.numel() * red.element_size() < 4 * n:
+            raise ValueError("fanout_device_red: red holds fewer than n records")
+        if red_out is not None and (red_out.element_size() != 1 or red_out.numel() < n):
+            raise ValueError("fanout_device_red: red_out holds fewer than n 1-byte elements")
+        if np.isscalar(tid):
+            tids_p, tid0 = None, int(tid)
+        else:
+            tids_p, tid0 = tid.data_ptr(), -1
+        sp = getattr(stream, "cuda_stream", stream)
+        rc = N.lib().srtp_fanout_device_red(
+            self.h, src_seg.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), src_cap.data_ptr(),
+            None if src_status is None else src_status.data_ptr(), m, src_idx.data_ptr(), tids_p, tid0,
+            seg.data_ptr(), off.data_ptr(), length.data_ptr(), cap.data_ptr(),
+            None if flags is None else flags.data_ptr(), None if rewrite is None else rewrite.data_ptr(),
+            None if stamp is None else stamp.data_ptr(), None if pay is None else pay.data_ptr(),
+            None if red is None else red.data_ptr(), None if red_out is None else red_out.data_ptr(),
+            status.data_ptr(), n, sp)
+        N.check(rc, self.h, "srtp_fanout_device_red")
+
     def fanout_host(self, tid, src_seg: np.ndarray, src_off, src_len, src_cap, src_idx, seg: np.ndarray, off,
                     cap, src_status=None, flags=None):
         """srtp_fanout_host over numpy: only the source segment and the small
@@ -715,6 +762,67 @@ class SRTPEngine:
             None if ast is None else ast.ctypes.data, py.ctypes.data, status.ctypes.data, n)
         N.check(rc, self.h, "srtp_fanout_host_pay")
         return length, status
+
+    def fanout_host_red(self, tid, src_seg: np.ndarray, src_off, src_len, src_cap, src_idx, seg: np.ndarray, off,
+                        cap, src_status=None, flags=None, rewrite=None, stamp=None, pay=None, red=None):
+        """srtp_fanout_host_red: :meth:`fanout_host_pay` with one RED record
+        per destination entry, ``red`` a numpy structured array of n records
+        with dtype ``N.FANOUT_RED_DTYPE`` (None: :meth:`fanout_host_pay`
+        exactly, every result code 0); ``rewrite``, ``stamp`` and ``pay`` may
+        each be None.  What a record does is :meth:`fanout_device_red`'s
+        (REDFilterTransformEngine.java:95-145, REDTransformEngine.java:151-182).
+        A record with mode > 2, red_pt > 127 or non-zero reserved bytes is
+        refused (SRTP_EINVAL).  Returns ``(length, status, red_out)``,
+        ``red_out`` an int8 array."""
+        if red is None:
+            length, status = self.fanout_host_pay(tid, src_seg, src_off, src_len, src_cap, src_idx, seg, off, cap,
+                                                  src_status, flags, rewrite, stamp, pay)
+            return length, status, np.zeros(len(status), np.int8)
+        assert src_seg.dtype == np.uint8 and src_seg.flags.c_contiguous
+        assert seg.dtype == np.uint8 and seg.flags.c_contiguous and seg.flags.writeable
+        src_off = np.ascontiguousarray(src_off, np.uint32)
+        src_len = np.ascontiguousarray(src_len, np.uint32)
+        src_cap = np.ascontiguousarray(src_cap, np.uint32)
+        src_idx = np.ascontiguousarray(src_idx, np.int32)
+        off = np.ascontiguousarray(off, np.uint32)
+        cap = np.ascontiguousarray(cap, np.uint32)
+        m, n = len(src_off), len(off)
+        assert len(src_len) == m and len(src_cap) == m and len(src_idx) == n and len(cap) == n
+        st_in = None if src_status is None else np.ascontiguousarray(src_status, np.int32)
+        fl = None if flags is None else np.ascontiguousarray(flags, np.uint32)
+        assert (st_in is None or len(st_in) == m) and (fl is None or len(fl) == n)
+        rw = None if rewrite is None else np.ascontiguousarray(rewrite, N.FANOUT_REWRITE_DTYPE)
+        ast = None if stamp is None else np.ascontiguousarray(stamp, N.FANOUT_AST_DTYPE)
+        py = None if pay is None else np.ascontiguousarray(pay, N.FANOUT_PAYLOAD_DTYPE)
+        rd = np.ascontiguousarray(red, N.FANOUT_RED_DTYPE)
+        if len(rd) < n or (py is not None and len(py) < n):
+            raise ValueError("fanout_host_red: fewer than n records")
+        assert (rw is None or len(rw) == n) and (ast is None or len(ast) == n)
+        if np.isscalar(tid):
+            tids_p, tid0 = None, int(tid)
+        else:
+            tids = np.ascontiguousarray(tid, np.int32)
+            assert len(tids) == n
+            tids_p, tid0 = tids.ctypes.data, -1
+        length = np.zeros(n, np.uint32)
+        status = np.zeros(n, np.int32)
+        red_out = np.zeros(n, np.int8)
+        rc = N.lib().srtp_fanout_host_red(
+            self.h, src_seg.ctypes.data, src_seg.nbytes, src_off.ctypes.data, src_len.ctypes.data,
+            src_cap.ctypes.data, None if st_in is None else st_in.ctypes.data, m, src_idx.ctypes.data, tids_p,
+            tid0, seg.ctypes.data, seg.nbytes, off.ctypes.data, length.ctypes.data, cap.ctypes.data,
+            None if fl is None else fl.ctypes.data, None if rw is None else rw.ctypes.data,
+            None if ast is None else ast.ctypes.data, None if py is None else py.ctypes.data, rd.ctypes.data,
+            red_out.ctypes.data, status.ctypes.data, n)
+        N.check(rc, self.h, "srtp_fanout_host_red")
+        return length, status, red_out
+
+    def fanout_red_stats(self) -> dict:
+        """srtp_engine_fanout_red_stats: the _red calls with records, and the
+        entries they stripped, wrapped and dropped."""
+        st = N.FanoutRedStats()
+        N.check(N.lib().srtp_engine_fanout_red_stats(self.h, C.byref(st)), self.h, "fanout_red_stats")
+        return st.as_dict()
 
     def fanout_stats(self) -> dict:
         """srtp_engine_fanout_stats: fan-out calls, their sources and
@@ -1632,6 +1740,48 @@ def fan_out_pay(pkts: Sequence[Optional[RawPacket]], transformers: Sequence[_SRT
     return _fan_out(pkts, transformers, rewriters, exclusion, stampers, payload=True)
 
 
+RED_OFF, RED_STRIP, RED_WRAP = N.RED_OFF, N.RED_STRIP, N.RED_WRAP
+
+
+def fan_out_red(pkts: Sequence[Optional[RawPacket]], transformers: Sequence[_SRTPBase], rewriters, stampers, payers,
+                reds, exclusion=None):
+    """:func:`fan_out_pay` for a bridge whose peers differ in whether they
+    negotiated RED (RFC 2198).  ``reds`` holds one ``(mode, red_pt)`` (or None)
+    per transformer: ``RED_STRIP`` is REDFilterTransformEngine.transform
+    (transform/REDFilterTransformEngine.java:95-145), which takes the one-byte
+    RED header out of a single-block packet whose PT is ``red_pt``;
+    ``RED_WRAP`` is REDTransformEngine.transform (transform/
+    REDTransformEngine.java:151-182), which puts one in and makes ``red_pt`` the
+    PT; ``RED_OFF`` or None leaves the peer's copies alone.  A packet on which
+    the reference throws is lost for that peer (None), as there.
+
+    ``payers`` holds one callable (or None) per transformer: ``payer(pkt)``
+    returns None or a mapping with ``osn`` and / or ``fec``, :func:`fan_out_pay`'s
+    two keys, here apart from the header fields so that a peer may have one
+    without the other.  RED runs first (MediaStreamImpl.java:993-998): ``osn`` is
+    written at the header's end, which RED does not move, and ``fec``'s offset
+    counts in the packet RED left.  A rewriter's mapping may still carry both.
+
+    The copies are made, changed and protected on the GPU
+    (srtp_fanout_host_red).  Returns ``(out, codes)``: ``out`` as
+    :func:`fan_out_pay`'s, ``codes[k][i]`` what RED did to packet i for
+    transformer k (0 untouched, 1 stripped, 2 wrapped, -1 dropped)."""
+    transformers, rewriters, stampers = list(transformers), list(rewriters), list(stampers)
+    payers, reds = list(payers), list(reds)
+    if len(rewriters) != len(transformers):
+        raise ValueError("fan_out_red: one rewriter (or None) per transformer")
+    if len(stampers) != len(transformers):
+        raise ValueError("fan_out_red: one stamper (or None) per transformer")
+    if len(payers) != len(transformers):
+        raise ValueError("fan_out_red: one payer (or None) per transformer")
+    if len(reds) != len(transformers):
+        raise ValueError("fan_out_red: one (mode, red_pt) (or None) per transformer")
+    for x in reds:
+        if x is not None and not (int(x[0]) in (RED_OFF, RED_STRIP, RED_WRAP) and 0 <= int(x[1]) <= 127):
+            raise ValueError("fan_out_red: a RED record of %r" % (x,))
+    return _fan_out(pkts, transformers, rewriters, exclusion, stampers, payload=True, payers=payers, reds=reds)
+
+
 def _pay_one(pay, j, r, p):
     """Entry j's payload record from the rewriter's mapping r: fec is patch 0, osn patch 1."""
     if "fec" in r:
@@ -1663,11 +1813,11 @@ def _stamp_one(stamp, j, g, p):
     stamp["id"][j], stamp["value"][j], stamp["on"][j] = int(ext_id), int(value) & 0x00FFFFFF, 1
 
 
-def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None, payload=False):
+def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None, payload=False, payers=None, reds=None):
     pkts, transformers = list(pkts), list(transformers)
     out = [[None] * len(pkts) for _ in transformers]
     if not pkts or not transformers:
-        return out
+        return out if reds is None else (out, [[0] * len(pkts) for _ in transformers])
     eng = transformers[0].engine
     if not isinstance(eng, SRTPEngine) or any(t.engine is not eng for t in transformers):
         raise ValueError("fan_out: the transformers of one SRTPEngine")
@@ -1680,6 +1830,8 @@ def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None, payload=Fa
     tids = np.tile(np.array([t.tid for t in transformers], np.int32), len(pkts))
     # a copy's buffer holds the packet and the trailer (RawPacket.append / grow)
     cap = np.repeat(np.maximum(src_cap, src_len + room), T).astype(np.uint32)
+    if reds is not None:  # a wrapped copy is one byte longer (REDTransformEngine allocates len + 1)
+        cap += np.tile(np.array([x is not None and int(x[0]) == RED_WRAP for x in reds], np.uint32), len(pkts))
     flags = np.repeat(src_flags & (N.PKT_FLAG_DISCARD | N.PKT_FLAG_SILENCE), T).astype(np.uint32)
     for i, x in enumerate(excl):
         for k, t in enumerate(transformers):
@@ -1718,6 +1870,20 @@ def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None, payload=Fa
                         rewrite[name][j] = int(r[name]) & lim
                         rewrite["mask"][j] |= bit
                 _stamp_one(stamp, j, g, p)
+    if payers is not None and any(y is not None for y in payers):
+        if pay is None:
+            pay = np.zeros(len(pkts) * T, N.FANOUT_PAYLOAD_DTYPE)
+        for i, p in enumerate(pkts):
+            for k in range(T):
+                j = i * T + k
+                if p is None or flags[j] & N.PKT_FLAG_SKIP or payers[k] is None:
+                    continue
+                y = payers[k](p)
+                if y is None:
+                    continue
+                if set(y) - {"osn", "fec"}:
+                    raise ValueError("fan_out_red: a payer returned %s" % sorted(set(y) - {"osn", "fec"}))
+                _pay_one(pay, j, y, p)
     step = (cap.astype(np.int64) + 15) & ~15
     off = np.concatenate(([0], np.cumsum(step)[:-1])).astype(np.int64)
     if int(off[-1] + step[-1]) >= 1 << 32:
@@ -1725,13 +1891,25 @@ def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None, payload=Fa
     seg = np.zeros(int(off[-1] + step[-1]), np.uint8)
     if pay is not None and not (pay["at0"].any() or pay["at1"].any()):
         pay = None  # no rewriter named a payload value: fan_out_ast's call
-    ln, st = eng.fanout_host_pay(tids, src_seg, src_off, src_len, src_cap, src_idx, seg, off.astype(np.uint32), cap,
-                                 src_status, flags, rewrite, stamp, pay)
+    codes = None
+    if reds is None:
+        ln, st = eng.fanout_host_pay(tids, src_seg, src_off, src_len, src_cap, src_idx, seg, off.astype(np.uint32),
+                                     cap, src_status, flags, rewrite, stamp, pay)
+    else:
+        red = None
+        if any(x is not None and int(x[0]) != RED_OFF for x in reds):
+            red = np.zeros(len(pkts) * T, N.FANOUT_RED_DTYPE)
+            for k, x in enumerate(reds):
+                if x is not None:
+                    red["mode"][k::T], red["red_pt"][k::T] = int(x[0]), int(x[1])
+        ln, st, ro = eng.fanout_host_red(tids, src_seg, src_off, src_len, src_cap, src_idx, seg,
+                                         off.astype(np.uint32), cap, src_status, flags, rewrite, stamp, pay, red)
+        codes = [[int(ro[i * T + k]) for i in range(len(pkts))] for k in range(T)]
     for j in np.nonzero(st == N.STATUS_OK)[0]:
         i, k = divmod(int(j), T)
         o = int(off[j])
         out[k][i] = RawPacket(seg[o:o + int(ln[j])].tobytes(), 0, int(ln[j]), pkts[i].flags)
-    return out
+    return out if reds is None else (out, codes)
 
 
 def audio_level_job(pkt: bytes, length: int, cap: int, flags: int, ext_id: int):
