@@ -596,6 +596,93 @@ int srtp_fanout_red_job(const uint8_t *pkt, int32_t src_idx, int32_t m, int32_t 
                         int32_t src_status, int32_t dst_cap, uint32_t flags, const srtp_fanout_red *red,
                         srtp_fanout_red_plan *out);
 
+/* Fan-out that makes ulpfec packets (RFC 5109, one level, short mask) per
+ * destination: the last engine in front of SRTP whose work grows with the
+ * payload, FECTransformEngine with its FECSender (transform/fec/FECSender.java,
+ * in the chain at MediaStreamImpl.java:988-991).  A destination entry can be an
+ * FEC entry: it has no source (src_idx[j] == -1), is made from up to 16 member
+ * entries of the same call and is then protected like any other entry.  Its
+ * plaintext is, byte for byte, what FECSender.FECPacket yields when addMedia is
+ * called on the members in list order and then finish() (:319-412), the
+ * members taken as they stand in the destination segment behind all their
+ * records (RED, rewrite, pay, stamp) and in front of the protect chain:
+ *   bytes 0-11   0x80, pt & 0x7F, the last member's sequence number + 1, the
+ *                last member's timestamp, ssrc
+ *   bytes 12-19  the XOR of the members' bytes 0-7, bytes 14-15 then the first
+ *                member's sequence number (SN base)
+ *   bytes 20-25  the XOR of len - 12, max(len - 12) (the protection length),
+ *                ((1 << count) - 1) << (16 - count)
+ *   bytes 26..   the XOR of the members' bytes from 12 on, a shorter member
+ *                contributing zeros; the length is 26 + the protection length
+ * mode SRTP_FEC_RED applies REDTransformEngine.transform to that packet (byte 12
+ * = pt, byte 1 = red_pt, everything from byte 12 on one byte up, length + 1).
+ * The reference runs the FEC engine in front of RED and SSRC rewriting and
+ * repairs only the SN base afterwards; here the XOR is over the packets the
+ * peer gets, as if the engine stood directly in front of SRTP.  For a peer
+ * without records the two coincide.  fec_job.h states the rule line by line.
+ *
+ * members[first .. first + count) are indices of destination entries.  An entry
+ * whose record is on is refused -- len[j] = 0, SKIP in the engine's flags word,
+ * SRTP_STATUS_SKIPPED, no context touched -- when count is outside 1..16, first
+ * + count > n_members, pt > 127, red_pt > 127 with mode 2, mode > 2, its own
+ * src_idx is not -1 (what the expansion copied there stays in its region), or a
+ * member is outside [0, n), has a record that is on, carries SKIP after the
+ * expansion, has not 12 <= len <= cap, or is not version 2.  A made entry's own
+ * rewrite, stamp, pay and red records are ignored; len[j] is 26 (27) + the
+ * protection length even past cap[j]: then only the bytes below cap[j] rounded
+ * up to 16 are stored and the entry ends SRTP_STATUS_DROP_INVALID like a
+ * host-made copy.  Two FEC entries may share members. */
+#define SRTP_FEC_OFF 0
+#define SRTP_FEC_PLAIN 1
+#define SRTP_FEC_RED 2
+typedef struct { uint32_t first, ssrc; uint8_t count, pt, red_pt, mode; } srtp_fanout_fec;
+/* fec_out[j]: 0 the record is off or the caller flagged the entry SKIP */
+#define SRTP_FEC_NONE 0
+#define SRTP_FEC_MADE 1
+#define SRTP_FEC_REFUSED (-1)
+/* srtp_fanout_device_red / srtp_fanout_host_red with four more arguments after
+ * red_out: fec, n records; members and n_members; fec_out, n result codes (may
+ * be NULL).  fec == NULL is the _red call, exactly.  Device route: fec and
+ * members are device arrays, 4-byte aligned (else SRTP_EINVAL before any
+ * launch); nothing is read back.  Host route: src_idx[j] == -1 is accepted
+ * exactly for entries whose record is on; a record or member that the rule
+ * would refuse for its fields or indices is SRTP_EINVAL with nothing launched;
+ * fec_out is copied back with len and status. */
+int srtp_fanout_device_fec(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
+                           const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status,
+                           uint32_t m, const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                           const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                           const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
+                           const srtp_fanout_payload *pay, const srtp_fanout_red *red, int8_t *red_out,
+                           const srtp_fanout_fec *fec, const int32_t *members, uint32_t n_members,
+                           int8_t *fec_out, int32_t *status, uint32_t n, void *stream);
+int srtp_fanout_host_fec(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_bytes, const uint32_t *src_off,
+                         const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status,
+                         uint32_t m, const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                         size_t seg_bytes, const uint32_t *off, uint32_t *len, const uint32_t *cap,
+                         const uint32_t *flags, const srtp_fanout_rewrite *rewrite,
+                         const srtp_fanout_abs_send_time *stamp, const srtp_fanout_payload *pay,
+                         const srtp_fanout_red *red, int8_t *red_out, const srtp_fanout_fec *fec,
+                         const int32_t *members, uint32_t n_members, int8_t *fec_out, int32_t *status,
+                         uint32_t n);
+/* Counters of the _fec calls with fec set, cumulative since engine creation:
+ * the calls, the entries made and refused, and the member bytes XORed (len - 4
+ * per member of a made entry: eight header bytes and the payload).
+ * srtp_fanout_stats.skipped does not count entries whose record is on. */
+typedef struct {
+    uint64_t calls, made, refused, member_bytes;
+} srtp_fanout_fec_stats;
+int srtp_engine_fanout_fec_stats(srtp_engine *e, srtp_fanout_fec_stats *out);
+/* The FEC rule of one entry (host only; fec_job.h, the text k_fanout_fec
+ * compiles) over the caller's member bytes: member i is bytes[at[i] .. at[i] +
+ * lens[i]), i < rec->count, with no flag, no record and cap = lens[i]; the
+ * entry's own src_idx is -1 and n_members is rec->first + rec->count.  *code
+ * gets SRTP_FEC_MADE or SRTP_FEC_REFUSED (SRTP_FEC_NONE for mode 0), *len_out
+ * the packet's length, and out[0 .. min(*len_out, out_cap)) its bytes, built
+ * piece by piece as the kernel builds them. */
+int srtp_fanout_fec_job(const srtp_fanout_fec *rec, const uint8_t *bytes, const uint32_t *at, const uint32_t *lens,
+                        uint8_t *out, uint32_t out_cap, int32_t *len_out, int8_t *code);
+
 /* The engine's own non-blocking stream, created with the engine so that each
  * engine gets a hardware queue of its own (streams created later may share
  * one, which serialises them): srtp_transform_host and the pipeline run their

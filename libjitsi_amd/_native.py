@@ -97,6 +97,7 @@ EXPORTED = [
     "srtp_transform_device_lvl", "srtp_transform_host_lvl", "srtp_engine_audio_level_stats",
     "srtp_audio_level_job",
     "srtp_fanout_device_red", "srtp_fanout_host_red", "srtp_engine_fanout_red_stats", "srtp_fanout_red_job",
+    "srtp_fanout_device_fec", "srtp_fanout_host_fec", "srtp_engine_fanout_fec_stats", "srtp_fanout_fec_job",
 ]
 STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 
@@ -104,7 +105,7 @@ STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 # Sources that decide what the crypto kernels execute: the key that ties
 # committed PMC counters (profiles/pmc_traffic.json) to the build they measured.
 KERNEL_SOURCES = ["srtp_kernels.hip", "aes_rounds_asm.inc", "srtp_kernels.h", "srtp_types.h", "engine.cpp",
-                  "gcm_job.h", "fanout_job.h", "bundle_plan.h", "audio_level_job.h", "red_job.h"]
+                  "gcm_job.h", "fanout_job.h", "bundle_plan.h", "audio_level_job.h", "red_job.h", "fec_job.h"]
 
 
 def kernel_source_sha16() -> str:
@@ -252,6 +253,27 @@ class FanoutRedPlan(C.Structure):
 class FanoutRedStats(C.Structure):
     """srtp_fanout_red_stats (include/srtp_mi355x.h)"""
     _fields_ = [(n, C.c_uint64) for n in ("calls", "stripped", "wrapped", "dropped")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class FanoutFec(C.Structure):
+    """srtp_fanout_fec (include/srtp_mi355x.h): one destination entry's FEC record"""
+    _fields_ = [("first", C.c_uint32), ("ssrc", C.c_uint32), ("count", C.c_uint8), ("pt", C.c_uint8),
+                ("red_pt", C.c_uint8), ("mode", C.c_uint8)]
+
+
+# numpy's view of an array of srtp_fanout_fec (fanout_host_fec)
+FANOUT_FEC_DTYPE = np.dtype([("first", "<u4"), ("ssrc", "<u4"), ("count", "u1"), ("pt", "u1"), ("red_pt", "u1"),
+                             ("mode", "u1")])
+FEC_OFF, FEC_PLAIN, FEC_RED = 0, 1, 2  # srtp_fanout_fec.mode
+FEC_NONE, FEC_MADE, FEC_REFUSED = 0, 1, -1  # fec_out
+
+
+class FanoutFecStats(C.Structure):
+    """srtp_fanout_fec_stats (include/srtp_mi355x.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "made", "refused", "member_bytes")]
 
     def as_dict(self) -> dict:
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -435,6 +457,13 @@ def lib() -> C.CDLL:
     L.srtp_fanout_red_job.argtypes = [vp, i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutRed),
                                       C.POINTER(FanoutRedPlan)]
     L.srtp_engine_fanout_red_stats.argtypes = [vp, C.POINTER(FanoutRedStats)]
+    L.srtp_fanout_device_fec.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                         vp, vp, vp, vp, u32, vp, vp, u32, vp]
+    L.srtp_fanout_host_fec.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, u32, vp, vp, i32, vp, C.c_size_t, vp, vp,
+                                       vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32]
+    L.srtp_fanout_fec_job.argtypes = [C.POINTER(FanoutFec), vp, vp, vp, vp, u32, C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int8)]
+    L.srtp_engine_fanout_fec_stats.argtypes = [vp, C.POINTER(FanoutFecStats)]
     L.srtp_engine_fanout_stats.argtypes = [vp, C.POINTER(FanoutStats)]
     L.srtp_fanout_job.argtypes = [i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutPlan)]
     L.srtp_transform_device_lvl.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, C.c_uint8, vp, vp, u32, vp]

@@ -22,6 +22,7 @@
 #include "audio_level_job.h"
 #include "fanout_job.h"
 #include "red_job.h"
+#include "fec_job.h"
 #include "gcm_job.h"
 #include "host_crypto.h"
 #include "srtp_kernels.h"
@@ -125,6 +126,12 @@ struct srtp_engine {
     int8_t *hs_red_out = nullptr;
     unsigned long long *d_red_stats = nullptr; // k_fanout_red's rows of entries stripped, wrapped, dropped
     uint64_t red_calls = 0;
+    srtp_fanout_fec *hs_fec = nullptr; // srtp_fanout_host_fec's records and result codes, staged like hs_red
+    int8_t *hs_fec_out = nullptr;
+    int32_t *hs_members = nullptr; // and its member indices, staged like hs_idx
+    uint32_t hs_fec_n = 0, hs_members_n = 0;
+    unsigned long long *d_fec_stats = nullptr; // k_fanout_fec's rows: made, refused, member bytes, on-entries skipped
+    uint64_t fec_calls = 0;
     uint32_t *hs_off = nullptr, *hs_len = nullptr, *hs_cap = nullptr;
     int32_t *hs_status = nullptr, *hs_idx = nullptr;
     uint64_t fan_calls = 0, fan_sources = 0, fan_destinations = 0, fan_src_bytes = 0;
@@ -636,7 +643,8 @@ void srtp_engine_destroy(srtp_engine *e) {
                     e->d_far, e->e_min, e->ctl, e->d_count, e->d_counters, e->h_seg, e->h_off, e->h_len,
                     e->h_cap, e->h_flags, e->h_status, e->h_tids, e->fan_flags, e->d_fan_skipped, e->hs_seg,
                     e->hs_off, e->hs_len, e->hs_cap, e->hs_status, e->hs_idx, e->hs_rw, e->hs_ast, e->hs_pay,
-                    e->hs_red, e->hs_red_out, e->d_red_stats, e->lvl_flags, e->d_lvl_stats, e->h_ext_ids, e->h_level};
+                    e->hs_red, e->hs_red_out, e->d_red_stats, e->hs_fec, e->hs_fec_out, e->hs_members,
+                    e->d_fec_stats, e->lvl_flags, e->d_lvl_stats, e->h_ext_ids, e->h_level};
     for (void *p : ptrs) dfree(p);
     if (e->ev_last) (void)hipEventDestroy(e->ev_last);
     if (e->ev_dev) (void)hipEventDestroy(e->ev_dev);
@@ -1097,6 +1105,7 @@ static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t 
                          const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
                          const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
                          const srtp_fanout_payload *pay, const srtp_fanout_red *red, int8_t *red_out,
+                         const srtp_fanout_fec *fec, const int32_t *members, uint32_t n_members, int8_t *fec_out,
                          int32_t *status, uint32_t n, hipStream_t s, bool dev_event) {
     int rc = check_fanout(e, {src_seg, src_off, src_len, src_cap, src_idx, seg, off, len, cap, status}, m, n);
     if (rc == SRTP_OK && ((uintptr_t)rewrite & 15u)) // k_fanout_rw loads a record in one 16-byte piece
@@ -1107,6 +1116,9 @@ static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t 
         rc = fail(e, SRTP_EINVAL, "pay must be 8-byte aligned");
     if (rc == SRTP_OK && ((uintptr_t)red & 3u)) // k_fanout_red loads a record in one 4-byte piece
         rc = fail(e, SRTP_EINVAL, "red must be 4-byte aligned");
+    if (rc == SRTP_OK && (((uintptr_t)fec & 3u) || (fec && ((uintptr_t)members & 3u)))) // k_fanout_fec loads words
+        rc = fail(e, SRTP_EINVAL, "fec and members must be 4-byte aligned");
+    if (rc == SRTP_OK && fec && n_members && !members) rc = fail(e, SRTP_EINVAL, "members is NULL");
     if (rc == SRTP_OK) rc = check_tid(e, tids != nullptr, tid);
     if (rc == SRTP_OK) rc = ensure_scratch(e, n);
     if (rc != SRTP_OK) return rc;
@@ -1128,6 +1140,10 @@ static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t 
         HIPCHK(e, dalloc(&e->d_red_stats, kRedStatReplicas * kRedStatStride));
         HIPCHK(e, hipMemsetAsync(e->d_red_stats, 0, kRedStatReplicas * kRedStatStride * sizeof(unsigned long long), s));
     }
+    if (fec && !e->d_fec_stats) {
+        HIPCHK(e, dalloc(&e->d_fec_stats, kFecStatReplicas * kFecStatStride));
+        HIPCHK(e, hipMemsetAsync(e->d_fec_stats, 0, kFecStatReplicas * kFecStatStride * sizeof(unsigned long long), s));
+    }
     if (e->have_last && e->last_stream != s) HIPCHK(e, hipStreamWaitEvent(s, last_event(e), 0));
     FanoutArgs f{};
     f.src_seg = src_seg; f.src_off = src_off; f.src_len = src_len; f.src_cap = src_cap;
@@ -1138,13 +1154,35 @@ static int fanout_locked(srtp_engine *e, const uint8_t *src_seg, const uint32_t 
     f.n = n;
     const FanRedArgs fr{reinterpret_cast<const uint32_t *>(red), red_out, e->d_red_stats};
     HIPCHK(e, launch_fanout(f, s, rewrite, stamp, pay, red ? &fr : nullptr));
+    if (fec) { // behind the expansion, in front of the chain: the members lie in the destination segment
+        const FanFecArgs fx{reinterpret_cast<const uint32_t *>(fec), members, n_members, fec_out, e->d_fec_stats};
+        HIPCHK(e, launch_fanout_fec(f, fx, s));
+    }
     rc = transform_locked(e, 0, tids, tid, seg, off, len, cap, e->fan_flags, status, n, s, -1, dev_event);
     if (rc != SRTP_OK) return rc;
     e->fan_calls++;
     e->fan_sources += m;
     e->fan_destinations += n;
     if (red) e->red_calls++;
+    if (fec) e->fec_calls++;
     return SRTP_OK;
+}
+
+int srtp_fanout_device_fec(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
+                           const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status, uint32_t m,
+                           const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg,
+                           const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                           const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
+                           const srtp_fanout_payload *pay, const srtp_fanout_red *red, int8_t *red_out,
+                           const srtp_fanout_fec *fec, const int32_t *members, uint32_t n_members,
+                           int8_t *fec_out, int32_t *status, uint32_t n, void *stream) {
+    if (!e) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (n == 0) return SRTP_OK;
+    GUARD(e);
+    return fanout_locked(e, src_seg, src_off, src_len, src_cap, src_status, m, src_idx, tids, tid, seg, off, len,
+                         cap, flags, rewrite, stamp, pay, red, red ? red_out : nullptr, fec, fec ? members : nullptr,
+                         fec ? n_members : 0u, fec ? fec_out : nullptr, status, n, (hipStream_t)stream, true);
 }
 
 int srtp_fanout_device_red(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
@@ -1154,13 +1192,9 @@ int srtp_fanout_device_red(srtp_engine *e, const uint8_t *src_seg, const uint32_
                            const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
                            const srtp_fanout_payload *pay, const srtp_fanout_red *red, int8_t *red_out,
                            int32_t *status, uint32_t n, void *stream) {
-    if (!e) return SRTP_EINVAL;
-    std::lock_guard<std::mutex> g(e->mu);
-    if (n == 0) return SRTP_OK;
-    GUARD(e);
-    return fanout_locked(e, src_seg, src_off, src_len, src_cap, src_status, m, src_idx, tids, tid, seg, off, len,
-                         cap, flags, rewrite, stamp, pay, red, red ? red_out : nullptr, status, n,
-                         (hipStream_t)stream, true);
+    return srtp_fanout_device_fec(e, src_seg, src_off, src_len, src_cap, src_status, m, src_idx, tids, tid, seg, off,
+                                  len, cap, flags, rewrite, stamp, pay, red, red_out, nullptr, nullptr, 0, nullptr,
+                                  status, n, stream);
 }
 
 int srtp_fanout_device_pay(srtp_engine *e, const uint8_t *src_seg, const uint32_t *src_off,
@@ -1246,6 +1280,40 @@ int srtp_fanout_host_red(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
                          const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
                          const srtp_fanout_payload *pay, const srtp_fanout_red *red, int8_t *red_out,
                          int32_t *status, uint32_t n) {
+    return srtp_fanout_host_fec(e, src_seg, src_seg_bytes, src_off, src_len, src_cap, src_status, m, src_idx, tids,
+                                tid, seg, seg_bytes, off, len, cap, flags, rewrite, stamp, pay, red, red_out, nullptr,
+                                nullptr, 0, nullptr, status, n);
+}
+
+// What the host route refuses of the FEC arguments before anything is launched: a record or a member that
+// fec_job.h's rule would refuse for its fields or indices.  Null: fine.
+static const char *fec_host_refusal(const int32_t *src_idx, uint32_t m, const srtp_fanout_fec *fec,
+                                    const int32_t *members, uint32_t n_members, uint32_t n) {
+    for (uint32_t j = 0; j < n; j++) {
+        const bool on = fec && fec[j].mode != SRTP_FEC_OFF;
+        if (!on) {
+            if (src_idx[j] < 0 || (uint32_t)src_idx[j] >= m) return "src_idx[j] names no source";
+            continue;
+        }
+        if (!fec_record_ok(fec[j].first, fec[j].count, fec[j].pt, fec[j].red_pt, fec[j].mode, n_members, src_idx[j]))
+            return "fec[j] has a field out of range, or src_idx[j] is not -1";
+        for (uint32_t k = 0; k < fec[j].count; k++) {
+            const int32_t mi = members[fec[j].first + k];
+            if (!fec_member_index_ok(mi, (int)n)) return "a member names no entry";
+            if (fec[mi].mode != SRTP_FEC_OFF) return "a member is an FEC entry";
+        }
+    }
+    return nullptr;
+}
+
+int srtp_fanout_host_fec(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_bytes, const uint32_t *src_off,
+                         const uint32_t *src_len, const uint32_t *src_cap, const int32_t *src_status, uint32_t m,
+                         const int32_t *src_idx, const int32_t *tids, int32_t tid, uint8_t *seg, size_t seg_bytes,
+                         const uint32_t *off, uint32_t *len, const uint32_t *cap, const uint32_t *flags,
+                         const srtp_fanout_rewrite *rewrite, const srtp_fanout_abs_send_time *stamp,
+                         const srtp_fanout_payload *pay, const srtp_fanout_red *red, int8_t *red_out,
+                         const srtp_fanout_fec *fec, const int32_t *members, uint32_t n_members,
+                         int8_t *fec_out, int32_t *status, uint32_t n) {
     if (!e) return SRTP_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
     if (n == 0) return SRTP_OK;
@@ -1253,8 +1321,9 @@ int srtp_fanout_host_red(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
     if (rc == SRTP_OK) rc = validate_regions(e, src_off, src_cap, m, src_seg_bytes);
     if (rc == SRTP_OK) rc = validate_regions(e, off, cap, n, seg_bytes);
     if (rc != SRTP_OK) return rc;
-    for (uint32_t j = 0; j < n; j++)
-        if (src_idx[j] < 0 || (uint32_t)src_idx[j] >= m) return fail(e, SRTP_EINVAL, "src_idx[j] names no source");
+    if (fec && n_members && !members) return fail(e, SRTP_EINVAL, "members is NULL");
+    if (!fec) n_members = 0;
+    if (const char *why = fec_host_refusal(src_idx, m, fec, members, n_members, n)) return fail(e, SRTP_EINVAL, why);
     for (uint32_t j = 0; rewrite && j < n; j++)
         if (rewrite[j].mask & ~kFanRewriteAll) return fail(e, SRTP_EINVAL, "rewrite[j].mask has a bit above 0xF");
     for (uint32_t j = 0; red && j < n; j++)
@@ -1269,7 +1338,7 @@ int srtp_fanout_host_red(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
     const size_t need = (src_seg_bytes + 15) & ~(size_t)15;
     if ((need > e->hs_seg_bytes || m > e->hs_m || n > e->hs_n || (rewrite && n > e->hs_rw_n) ||
          (stamp && n > e->hs_ast_n) || (pay && n > e->hs_pay_n) ||
-         (red && n > e->hs_red_n)) &&
+         (red && n > e->hs_red_n) || (fec && (n > e->hs_fec_n || n_members > e->hs_members_n))) &&
         e->have_last) {
         rc = quiesce(e); // the source staging may still be read by an enqueued fan-out
         if (rc != SRTP_OK) return rc;
@@ -1281,6 +1350,8 @@ int srtp_fanout_host_red(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
     if (rc == SRTP_OK && stamp) rc = grow_staging(e, &e->hs_ast_n, n, &e->hs_ast);
     if (rc == SRTP_OK && pay) rc = grow_staging(e, &e->hs_pay_n, n, &e->hs_pay);
     if (rc == SRTP_OK && red) rc = grow_staging(e, &e->hs_red_n, n, &e->hs_red, &e->hs_red_out);
+    if (rc == SRTP_OK && fec) rc = grow_staging(e, &e->hs_fec_n, n, &e->hs_fec, &e->hs_fec_out);
+    if (rc == SRTP_OK && fec) rc = grow_staging(e, &e->hs_members_n, std::max<uint32_t>(n_members, 1), &e->hs_members);
     if (rc != SRTP_OK) return rc;
     // only the source segment and the small arrays cross to the device
     HIPCHK(e, hipMemcpyAsync(e->hs_seg, src_seg, src_seg_bytes, hipMemcpyHostToDevice, s));
@@ -1293,6 +1364,9 @@ int srtp_fanout_host_red(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
     if (stamp) HIPCHK(e, hipMemcpyAsync(e->hs_ast, stamp, n * sizeof *stamp, hipMemcpyHostToDevice, s));
     if (pay) HIPCHK(e, hipMemcpyAsync(e->hs_pay, pay, n * sizeof *pay, hipMemcpyHostToDevice, s));
     if (red) HIPCHK(e, hipMemcpyAsync(e->hs_red, red, n * sizeof *red, hipMemcpyHostToDevice, s));
+    if (fec) HIPCHK(e, hipMemcpyAsync(e->hs_fec, fec, n * sizeof *fec, hipMemcpyHostToDevice, s));
+    if (fec && n_members)
+        HIPCHK(e, hipMemcpyAsync(e->hs_members, members, n_members * 4ull, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(e->h_off, off, n * 4ull, hipMemcpyHostToDevice, s));
     HIPCHK(e, hipMemcpyAsync(e->h_cap, cap, n * 4ull, hipMemcpyHostToDevice, s));
     if (flags) HIPCHK(e, hipMemcpyAsync(e->h_flags, flags, n * 4ull, hipMemcpyHostToDevice, s));
@@ -1301,13 +1375,15 @@ int srtp_fanout_host_red(srtp_engine *e, const uint8_t *src_seg, size_t src_seg_
                        e->hs_idx, tids ? e->h_tids : nullptr, tid, e->h_seg, e->h_off, e->h_len, e->h_cap,
                        flags ? e->h_flags : nullptr, rewrite ? e->hs_rw : nullptr, stamp ? e->hs_ast : nullptr,
                        pay ? e->hs_pay : nullptr, red ? e->hs_red : nullptr, red ? e->hs_red_out : nullptr,
-                       e->h_status, n, s, false);
+                       fec ? e->hs_fec : nullptr, fec ? e->hs_members : nullptr, n_members,
+                       fec ? e->hs_fec_out : nullptr, e->h_status, n, s, false);
     if (rc != SRTP_OK) return rc;
     e->fan_src_bytes += src_seg_bytes;
     HIPCHK(e, hipMemcpyAsync(seg, e->h_seg, seg_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipMemcpyAsync(len, e->h_len, n * 4ull, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipMemcpyAsync(status, e->h_status, n * 4ull, hipMemcpyDeviceToHost, s));
     if (red && red_out) HIPCHK(e, hipMemcpyAsync(red_out, e->hs_red_out, n, hipMemcpyDeviceToHost, s));
+    if (fec && fec_out) HIPCHK(e, hipMemcpyAsync(fec_out, e->hs_fec_out, n, hipMemcpyDeviceToHost, s));
     HIPCHK(e, hipStreamSynchronize(s));
     return SRTP_OK;
 }
@@ -1331,6 +1407,34 @@ int srtp_engine_fanout_red_stats(srtp_engine *e, srtp_fanout_red_stats *out) {
     return SRTP_OK;
 }
 
+// The rows of k_fanout_fec summed: made, refused, member bytes, on-entries the expansion counted as skipped.
+static int fec_stat_sums(srtp_engine *e, unsigned long long sums[4]) {
+    unsigned long long st[kFecStatReplicas * kFecStatStride];
+    HIPCHK(e, hipMemcpy(st, e->d_fec_stats, sizeof st, hipMemcpyDeviceToHost));
+    for (int k = 0; k < 4; k++) sums[k] = 0;
+    for (uint32_t r = 0; r < kFecStatReplicas; r++)
+        for (int k = 0; k < 4; k++) sums[k] += st[r * kFecStatStride + k];
+    return SRTP_OK;
+}
+
+int srtp_engine_fanout_fec_stats(srtp_engine *e, srtp_fanout_fec_stats *out) {
+    if (!e || !out) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    memset(out, 0, sizeof *out);
+    out->calls = e->fec_calls;
+    if (!e->d_fec_stats) return SRTP_OK; // no _fec call yet
+    GUARD(e);
+    int rc = quiesce(e);
+    if (rc != SRTP_OK) return rc;
+    unsigned long long sums[4];
+    rc = fec_stat_sums(e, sums);
+    if (rc != SRTP_OK) return rc;
+    out->made = sums[0];
+    out->refused = sums[1];
+    out->member_bytes = sums[2];
+    return SRTP_OK;
+}
+
 int srtp_engine_fanout_stats(srtp_engine *e, srtp_fanout_stats *out) {
     if (!e || !out) return SRTP_EINVAL;
     std::lock_guard<std::mutex> g(e->mu);
@@ -1346,6 +1450,12 @@ int srtp_engine_fanout_stats(srtp_engine *e, srtp_fanout_stats *out) {
     unsigned long long sk = 0;
     HIPCHK(e, hipMemcpy(&sk, e->d_fan_skipped, sizeof sk, hipMemcpyDeviceToHost));
     out->skipped = sk;
+    if (e->d_fec_stats) { // an FEC entry has no source: the expansion counted it, and it is none of these
+        unsigned long long sums[4];
+        rc = fec_stat_sums(e, sums);
+        if (rc != SRTP_OK) return rc;
+        out->skipped = sk - sums[3];
+    }
     return SRTP_OK;
 }
 
@@ -1448,6 +1558,70 @@ int srtp_fanout_red_job(const uint8_t *pkt, int32_t src_idx, int32_t m, int32_t 
     out->h = p.h;
     out->len_out = red_job(j, p, dst_cap).len_out;
     out->shift = p.shift;
+    return SRTP_OK;
+}
+
+int srtp_fanout_fec_job(const srtp_fanout_fec *rec, const uint8_t *bytes, const uint32_t *at, const uint32_t *lens,
+                        uint8_t *out, uint32_t out_cap, int32_t *len_out, int8_t *code) {
+    if (!rec || !len_out || !code) return SRTP_EINVAL;
+    static_assert(sizeof(srtp_fanout_fec) == 12 && offsetof(srtp_fanout_fec, ssrc) == 4 &&
+                      offsetof(srtp_fanout_fec, count) == 8 && offsetof(srtp_fanout_fec, pt) == 9 &&
+                      offsetof(srtp_fanout_fec, red_pt) == 10 && offsetof(srtp_fanout_fec, mode) == 11,
+                  "k_fanout_fec loads a record as three 32-bit words");
+    static_assert(SRTP_FEC_OFF == kFecOff && SRTP_FEC_PLAIN == kFecPlain && SRTP_FEC_RED == kFecRed &&
+                      SRTP_FEC_NONE == kFecNone && SRTP_FEC_MADE == kFecMade && SRTP_FEC_REFUSED == kFecRefused,
+                  "fec_job.h restates these constants");
+    *len_out = 0;
+    *code = SRTP_FEC_NONE;
+    if (rec->mode == SRTP_FEC_OFF) return SRTP_OK;
+    *code = SRTP_FEC_REFUSED;
+    if (!fec_record_ok(rec->first, rec->count, rec->pt, rec->red_pt, rec->mode, rec->first + (uint32_t)rec->count, -1))
+        return SRTP_OK;
+    if (!bytes || !at || !lens) return SRTP_EINVAL;
+    // a word of a member as the kernel loads it: bytes at or past len are whatever lies there (0xA5 here)
+    auto word = [&](uint32_t k, int w) {
+        uint32_t v = 0;
+        for (int b = 0; b < 4; b++) {
+            const int i = 4 * w + b;
+            v |= (uint32_t)(i < (int)lens[k] ? bytes[at[k] + i] : 0xA5u) << (8 * b);
+        }
+        return v;
+    };
+    FecHead h{};
+    for (uint32_t k = 0; k < rec->count; k++) {
+        if (lens[k] > (uint32_t)kFanMaxRegion || !fec_member_ok(0, 0, (int)lens[k], (int)lens[k])) return SRTP_OK;
+        const uint32_t w0 = word(k, 0), w1 = word(k, 1);
+        if (!fec_member_v2(w0)) return SRTP_OK;
+        const int l = (int)lens[k] - kFanHeaderBytes;
+        h.x0 ^= w0;
+        h.x1 ^= w1;
+        h.len_xor ^= l;
+        h.plen = l > h.plen ? l : h.plen;
+        if (k == 0) h.first_w0 = w0;
+        h.last_w0 = w0;
+        h.last_w1 = w1;
+    }
+    h.count = rec->count;
+    h.mode = rec->mode;
+    h.ssrc = rec->ssrc;
+    h.pt = rec->pt;
+    h.red_pt = rec->red_pt;
+    *code = SRTP_FEC_MADE;
+    *len_out = fec_len_out(h);
+    const int store = fec_store_bytes(*len_out, out_cap > (uint32_t)kFanMaxRegion ? kFanMaxRegion : (int)out_cap);
+    if (store && !out) return SRTP_EINVAL;
+    for (int q = 0; q < store / 16; q++) {
+        FecWindow a{0, 0, 0, 0, 0};
+        for (uint32_t k = 0; k < rec->count; k++) {
+            const int len = (int)lens[k], p = fec_src_piece(q, len);
+            fec_accumulate(a, FanoutPiece{word(k, 4 * p), word(k, 4 * p + 1), word(k, 4 * p + 2), word(k, 4 * p + 3)},
+                           word(k, fec_src_word(q, len)), q, len);
+        }
+        const FanoutPiece o = fec_piece(a, q, h);
+        const uint32_t w[4] = {o.w0, o.w1, o.w2, o.w3};
+        for (int b = 0; b < 16; b++) // the caller's buffer ends at out_cap, not at a piece's end
+            if ((uint32_t)(16 * q + b) < out_cap && 16 * q + b < *len_out) out[16 * q + b] = (uint8_t)(w[b / 4] >> (8 * (b % 4)));
+    }
     return SRTP_OK;
 }
 

@@ -202,6 +202,28 @@ struct FanRedArgs {
 };
 hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s, const void *rewrite = nullptr,
                          const void *stamp = nullptr, const void *pay = nullptr, const FanRedArgs *red = nullptr);
+// srtp_fanout_*_fec: behind the expansion and in front of the protect chain, a
+// wave per entry makes the ulpfec packet of every entry whose record is on
+// (k_fanout_fec, the rule in fec_job.h) from its members' bytes in the
+// destination segment.  `f` is the expansion's: off, cap, the caller's flags,
+// src_idx, m and src_status are read, len and flags_out of FEC entries are
+// written (made: the packet's length and the caller's flags; refused: 0 and
+// SKIP), and seg inside made entries' regions.  fec: n 12-byte records
+// (srtp_fanout_fec as three words: first, ssrc, count | pt << 8 | red_pt << 16
+// | mode << 24), 4-byte aligned; members: n_members indices, 4-byte aligned;
+// fec_out: null or n result codes; stats: kFecStatReplicas rows of
+// kFecStatStride words (64 bytes): a wave adds its entries made and refused,
+// the member bytes it XORed and the on-entries the expansion counted as skipped
+// by their source to words 0..3 of one row, and the host sums the rows.
+constexpr uint32_t kFecStatReplicas = 64, kFecStatStride = 8;
+struct FanFecArgs {
+    const uint32_t *fec;
+    const int32_t *members;
+    uint32_t n_members;
+    int8_t *fec_out;
+    unsigned long long *stats; // [kFecStatReplicas][kFecStatStride]
+};
+hipError_t launch_fanout_fec(const FanoutArgs &f, const FanFecArgs &x, hipStream_t s);
 // srtp_transform_device_lvl: in front of the unprotect chain, entry j's
 // ssrc-audio-level is read and its flags word made (k_audio_level, the rule in
 // audio_level_job.h): level[j] = the level (0..127) or -128, flags_out[j] =

@@ -65,6 +65,7 @@
 #include "../../include/srtp_mi355x.h"
 #include "audio_level_job.h"
 #include "fanout_job.h"
+#include "fec_job.h"
 #include "gcm_job.h"
 #include "red_job.h"
 #include "srtp_kernels.h"
@@ -7716,6 +7717,154 @@ hipError_t launch_fanout(const FanoutArgs &f, hipStream_t s, const void *rewrite
         hipLaunchKernelGGL(k_fanout_rw, dim3(wgs), dim3(kGatherBlock), 0, s, f, static_cast<const uint4 *>(rewrite));
     else
         hipLaunchKernelGGL(k_fanout, dim3(wgs), dim3(kGatherBlock), 0, s, f);
+    return hipGetLastError();
+}
+
+// The FEC pass (k_fanout_fec, srtp_fanout_*_fec): behind the expansion, a wave
+// per entry.  An entry whose record is off costs its wave one scalar load.  For
+// an entry whose record is on, fec_record_ok is asked with the record, the
+// entry's own source index and n_members alone; then lanes 0 .. count - 1 each
+// take one member: its index, and only where that lies in [0, n) its flags word
+// after the expansion, its own record's mode, len and cap, and only where
+// fec_member_ok passes on those (12 <= len <= cap: the region owns its first
+// 16 bytes) its first two words.  A ballot gives the verdict, the same in every
+// lane, before any other pointer into the segment is formed; a refused entry
+// forms none.  The header's scalars are reduced over readlane, which also hands
+// every lane each member's offset and length as wave-uniform values.
+//
+// Then lanes stride over the packet's 16-byte pieces.  Piece q takes of each
+// member the aligned piece and the aligned word fec_src_piece / fec_src_word
+// name (clamped to piece 0 / word 0 where the window leaves the member, and
+// masked there), four members to a batch: eight unconditional loads, then the
+// masks and XORs (fec_accumulate), and one funnel and store per piece
+// (fec_piece; pieces 0 and 1 take the header).
+//
+// Bounds.  loads: below each member's len rounded up to 16, at most its cap
+// rounded up to 16.  stores: pieces below fec_store_bytes = min(len_out, cap[j])
+// rounded up to 16 of entry j's own region, and len[j], flags_out[j],
+// fec_out[j] of entries whose record is on (fec_out[j] of every entry).  A
+// member is an entry whose record is off: no wave writes what another reads.
+__global__ __launch_bounds__(kGatherBlock) void k_fanout_fec(FanoutArgs f, FanFecArgs x) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (kGatherBlock / 64) + (threadIdx.x >> 6));
+    const uint32_t waves = gridDim.x * (kGatherBlock / 64);
+    uint32_t n_made = 0u, n_refused = 0u, n_sub = 0u; // the wave's, the same in every lane
+    unsigned long long n_bytes = 0ull;
+    for (uint32_t j = wave; j < f.n; j += waves) {
+        const uint32_t r2 = __builtin_amdgcn_readfirstlane(x.fec[3u * j + 2u]);
+        const uint32_t mode = r2 >> 24;
+        if (mode == 0u) {
+            if (lane == 0u && x.fec_out) x.fec_out[j] = (int8_t)kFecNone;
+            continue;
+        }
+        const int si = __builtin_amdgcn_readfirstlane(f.src_idx[j]);
+        const uint32_t fl = f.flags ? __builtin_amdgcn_readfirstlane(f.flags[j]) : 0u;
+        const bool in = si >= 0 && si < (int)f.m;
+        const int st = in && f.src_status ? __builtin_amdgcn_readfirstlane(f.src_status[si]) : 0;
+        n_sub += (!in || st != kFanStatusOk) ? 1u : 0u; // fanout_job's by_source: the expansion counted it
+        if (fl & kFanFlagSkip) { // the caller's: the expansion has left it skipped
+            if (lane == 0u && x.fec_out) x.fec_out[j] = (int8_t)kFecNone;
+            continue;
+        }
+        const uint32_t first = __builtin_amdgcn_readfirstlane(x.fec[3u * j]);
+        const uint32_t ssrc = __builtin_amdgcn_readfirstlane(x.fec[3u * j + 1u]);
+        const uint32_t count = r2 & 0xFFu, pt = (r2 >> 8) & 0xFFu, red_pt = (r2 >> 16) & 0xFFu;
+        const bool rec_ok = fec_record_ok(first, count, pt, red_pt, mode, x.n_members, si);
+        uint32_t moff = 0u, w0 = 0u, w1 = 0u;
+        int mlen = 0;
+        bool mok = false;
+        if (rec_ok && lane < count) {
+            const int mi = x.members[first + lane];
+            if (fec_member_index_ok(mi, (int)f.n)) {
+                const uint32_t mfl = f.flags_out[mi], mmode = x.fec[3u * (uint32_t)mi + 2u] >> 24;
+                const int ml = (int)f.len[mi], mc = (int)f.cap[mi];
+                if (fec_member_ok(mfl, mmode, ml, mc)) {
+                    moff = f.off[mi];
+                    mlen = ml;
+                    const uint2 hd = *reinterpret_cast<const uint2 *>(f.seg + moff);
+                    w0 = hd.x;
+                    w1 = hd.y;
+                    mok = fec_member_v2(w0);
+                }
+            }
+        }
+        const unsigned long long good = __ballot(mok);
+        const bool made = rec_ok && good == ((1ull << count) - 1ull); // count <= 16 where rec_ok
+        if (!made) {
+            if (lane == 0u) {
+                f.len[j] = 0u;
+                f.flags_out[j] = fl | kFanFlagSkip;
+                if (x.fec_out) x.fec_out[j] = (int8_t)kFecRefused;
+            }
+            n_refused++;
+            continue;
+        }
+        FecHead h;
+        h.x0 = 0u;
+        h.x1 = 0u;
+        h.len_xor = 0;
+        h.plen = 0;
+        for (uint32_t k = 0u; k < count; k++) {
+            const int l = __builtin_amdgcn_readlane(mlen, (int)k) - kFanHeaderBytes;
+            h.x0 ^= (uint32_t)__builtin_amdgcn_readlane((int)w0, (int)k);
+            h.x1 ^= (uint32_t)__builtin_amdgcn_readlane((int)w1, (int)k);
+            h.len_xor ^= l;
+            h.plen = max(h.plen, l);
+            n_bytes += (unsigned long long)(l + 8);
+        }
+        h.first_w0 = (uint32_t)__builtin_amdgcn_readlane((int)w0, 0);
+        h.last_w0 = (uint32_t)__builtin_amdgcn_readlane((int)w0, (int)count - 1);
+        h.last_w1 = (uint32_t)__builtin_amdgcn_readlane((int)w1, (int)count - 1);
+        h.count = (int)count;
+        h.mode = (int)mode;
+        h.ssrc = ssrc;
+        h.pt = pt;
+        h.red_pt = red_pt;
+        const int len_out = fec_len_out(h);
+        if (lane == 0u) {
+            f.len[j] = (uint32_t)len_out;
+            f.flags_out[j] = fl;
+            if (x.fec_out) x.fec_out[j] = (int8_t)kFecMade;
+        }
+        n_made++;
+        const uint32_t wd = (uint32_t)fec_store_bytes(len_out, (int)f.cap[j]) / 16u;
+        if (wd == 0u) continue; // nothing to store: no destination pointer is formed
+        uint4 *t = reinterpret_cast<uint4 *>(f.seg + f.off[j]);
+        for (uint32_t q = lane; q < wd; q += 64u) {
+            FecWindow a = {0u, 0u, 0u, 0u, 0u};
+            for (uint32_t k0 = 0u; k0 < count; k0 += 4u) {
+                uint4 P[4];
+                uint32_t W[4];
+                int L[4];
+#pragma unroll
+                for (uint32_t i = 0u; i < 4u; i++) { // a slot past the last member reads the last one's piece 0, masked
+                    const uint32_t k = min(k0 + i, count - 1u);
+                    const uint8_t *mb = f.seg + (uint32_t)__builtin_amdgcn_readlane((int)moff, (int)k);
+                    L[i] = k0 + i < count ? __builtin_amdgcn_readlane(mlen, (int)k) : 0;
+                    P[i] = reinterpret_cast<const uint4 *>(mb)[fec_src_piece((int)q, L[i])];
+                    W[i] = reinterpret_cast<const uint32_t *>(mb)[fec_src_word((int)q, L[i])];
+                }
+#pragma unroll
+                for (uint32_t i = 0u; i < 4u; i++)
+                    fec_accumulate(a, FanoutPiece{P[i].x, P[i].y, P[i].z, P[i].w}, W[i], (int)q, L[i]);
+            }
+            const FanoutPiece o = fec_piece(a, (int)q, h);
+            t[q] = uint4{o.w0, o.w1, o.w2, o.w3};
+        }
+    }
+    if (lane == 0u) { // one of kFecStatReplicas rows, by wave, as k_audio_level's
+        unsigned long long *row = x.stats + kFecStatStride * (wave % kFecStatReplicas);
+        if (n_made) atomicAdd(row + 0, (unsigned long long)n_made);
+        if (n_refused) atomicAdd(row + 1, (unsigned long long)n_refused);
+        if (n_bytes) atomicAdd(row + 2, n_bytes);
+        if (n_sub) atomicAdd(row + 3, (unsigned long long)n_sub);
+    }
+}
+
+hipError_t launch_fanout_fec(const FanoutArgs &f, const FanFecArgs &x, hipStream_t s) {
+    if (f.n == 0) return hipSuccess;
+    const uint32_t wgs = std::min<uint32_t>((f.n + 3u) / 4u, 4096u); // an entry per wave
+    hipLaunchKernelGGL(k_fanout_fec, dim3(wgs), dim3(kGatherBlock), 0, s, f, x);
     return hipGetLastError();
 }
 

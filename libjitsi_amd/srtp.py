@@ -625,6 +625,52 @@ class SRTPEngine:
             status.data_ptr(), n, sp)
         N.check(rc, self.h, "srtp_fanout_device_red")
 
+    def fanout_device_fec(self, tid, src_seg, src_off, src_len, src_cap, src_idx, seg, off, length, cap, status,
+                          rewrite, stamp, pay, red, red_out, fec, members, fec_out, src_status=None, flags=None,
+                          m: Optional[int] = None, n: Optional[int] = None, n_members: Optional[int] = None,
+                          stream=None) -> None:
+        """srtp_fanout_device_fec: :meth:`fanout_device_red` with one FEC
+        record per destination entry.  ``fec`` is a tensor on this engine's GPU
+        that holds n x 12 bytes, 4-byte aligned (n records of
+        ``N.FANOUT_FEC_DTYPE``: first, ssrc, count, pt, red_pt, mode), or None
+        for :meth:`fanout_device_red` exactly; ``members`` an int32 tensor of
+        ``n_members`` indices of destination entries.  An entry whose record is
+        on (``N.FEC_PLAIN``, ``N.FEC_RED``) has ``src_idx`` -1 and becomes the
+        ulpfec packet (FECSender.java:319-412) over entries ``members[first ..
+        first + count)`` as their other records left them, wrapped in RED
+        (REDTransformEngine.java:151-182) for ``N.FEC_RED``, and is protected
+        like any other entry; its own other records are ignored.  An entry the
+        rule refuses (include/srtp_mi355x.h lists the causes) ends
+        ``STATUS_SKIPPED``.  ``fec_out`` (None, or an int8 tensor of n
+        elements) gets ``N.FEC_NONE``, ``N.FEC_MADE`` or ``N.FEC_REFUSED``."""
+        if m is None:
+            m = src_off.numel()
+        if n is None:
+            n = off.numel()
+        if n_members is None:
+            n_members = 0 if members is None else members.numel()
+        for name, t, size in (("rewrite", rewrite, 16), ("stamp", stamp, 8), ("pay", pay, 8), ("red", red, 4),
+                              ("fec", fec, 12)):
+            if t is not None and t.numel() * t.element_size() < size * n:
+                raise ValueError("fanout_device_fec: %s holds fewer than n records" % name)
+        for name, t in (("red_out", red_out), ("fec_out", fec_out)):
+            if t is not None and (t.element_size() != 1 or t.numel() < n):
+                raise ValueError("fanout_device_fec: %s holds fewer than n 1-byte elements" % name)
+        if members is not None and members.numel() * members.element_size() < 4 * n_members:
+            raise ValueError("fanout_device_fec: members holds fewer than n_members indices")
+        if np.isscalar(tid):
+            tids_p, tid0 = None, int(tid)
+        else:
+            tids_p, tid0 = tid.data_ptr(), -1
+        sp = getattr(stream, "cuda_stream", stream)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        rc = N.lib().srtp_fanout_device_fec(
+            self.h, src_seg.data_ptr(), src_off.data_ptr(), src_len.data_ptr(), src_cap.data_ptr(), ptr(src_status),
+            m, src_idx.data_ptr(), tids_p, tid0, seg.data_ptr(), off.data_ptr(), length.data_ptr(), cap.data_ptr(),
+            ptr(flags), ptr(rewrite), ptr(stamp), ptr(pay), ptr(red), ptr(red_out), ptr(fec), ptr(members),
+            n_members, ptr(fec_out), status.data_ptr(), n, sp)
+        N.check(rc, self.h, "srtp_fanout_device_fec")
+
     def fanout_host(self, tid, src_seg: np.ndarray, src_off, src_len, src_cap, src_idx, seg: np.ndarray, off,
                     cap, src_status=None, flags=None):
         """srtp_fanout_host over numpy: only the source segment and the small
@@ -816,6 +862,70 @@ class SRTPEngine:
             red_out.ctypes.data, status.ctypes.data, n)
         N.check(rc, self.h, "srtp_fanout_host_red")
         return length, status, red_out
+
+    def fanout_host_fec(self, tid, src_seg: np.ndarray, src_off, src_len, src_cap, src_idx, seg: np.ndarray, off,
+                        cap, src_status=None, flags=None, rewrite=None, stamp=None, pay=None, red=None, fec=None,
+                        members=None):
+        """srtp_fanout_host_fec: :meth:`fanout_host_red` with one FEC record
+        per destination entry, ``fec`` a numpy structured array of n records
+        with dtype ``N.FANOUT_FEC_DTYPE`` and ``members`` an int32 array (None:
+        :meth:`fanout_host_red` exactly, every FEC code 0).  What a record does
+        is :meth:`fanout_device_fec`'s.  ``src_idx`` is -1 exactly for the
+        entries whose record is on; a record or member that the rule would
+        refuse for its fields or indices raises (SRTP_EINVAL).  Returns
+        ``(length, status, red_out, fec_out)``."""
+        if fec is None:
+            length, status, ro = self.fanout_host_red(tid, src_seg, src_off, src_len, src_cap, src_idx, seg, off,
+                                                      cap, src_status, flags, rewrite, stamp, pay, red)
+            return length, status, ro, np.zeros(len(status), np.int8)
+        assert src_seg.dtype == np.uint8 and src_seg.flags.c_contiguous
+        assert seg.dtype == np.uint8 and seg.flags.c_contiguous and seg.flags.writeable
+        src_off = np.ascontiguousarray(src_off, np.uint32)
+        src_len = np.ascontiguousarray(src_len, np.uint32)
+        src_cap = np.ascontiguousarray(src_cap, np.uint32)
+        src_idx = np.ascontiguousarray(src_idx, np.int32)
+        off = np.ascontiguousarray(off, np.uint32)
+        cap = np.ascontiguousarray(cap, np.uint32)
+        m, n = len(src_off), len(off)
+        assert len(src_len) == m and len(src_cap) == m and len(src_idx) == n and len(cap) == n
+        st_in = None if src_status is None else np.ascontiguousarray(src_status, np.int32)
+        fl = None if flags is None else np.ascontiguousarray(flags, np.uint32)
+        assert (st_in is None or len(st_in) == m) and (fl is None or len(fl) == n)
+        rw = None if rewrite is None else np.ascontiguousarray(rewrite, N.FANOUT_REWRITE_DTYPE)
+        ast = None if stamp is None else np.ascontiguousarray(stamp, N.FANOUT_AST_DTYPE)
+        py = None if pay is None else np.ascontiguousarray(pay, N.FANOUT_PAYLOAD_DTYPE)
+        rd = None if red is None else np.ascontiguousarray(red, N.FANOUT_RED_DTYPE)
+        fc = np.ascontiguousarray(fec, N.FANOUT_FEC_DTYPE)
+        mem = np.ascontiguousarray(np.zeros(0, np.int32) if members is None else members, np.int32)
+        for a in (rw, ast, py, rd, fc):
+            if a is not None and len(a) < n:
+                raise ValueError("fanout_host_fec: fewer than n records")
+        if np.isscalar(tid):
+            tids_p, tid0 = None, int(tid)
+        else:
+            tids = np.ascontiguousarray(tid, np.int32)
+            assert len(tids) == n
+            tids_p, tid0 = tids.ctypes.data, -1
+        length = np.zeros(n, np.uint32)
+        status = np.zeros(n, np.int32)
+        red_out = np.zeros(n, np.int8)
+        fec_out = np.zeros(n, np.int8)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = N.lib().srtp_fanout_host_fec(
+            self.h, src_seg.ctypes.data, src_seg.nbytes, src_off.ctypes.data, src_len.ctypes.data,
+            src_cap.ctypes.data, ptr(st_in), m, src_idx.ctypes.data, tids_p, tid0, seg.ctypes.data, seg.nbytes,
+            off.ctypes.data, length.ctypes.data, cap.ctypes.data, ptr(fl), ptr(rw), ptr(ast), ptr(py), ptr(rd),
+            red_out.ctypes.data, fc.ctypes.data, mem.ctypes.data if len(mem) else None, len(mem),
+            fec_out.ctypes.data, status.ctypes.data, n)
+        N.check(rc, self.h, "srtp_fanout_host_fec")
+        return length, status, red_out, fec_out
+
+    def fanout_fec_stats(self) -> dict:
+        """srtp_engine_fanout_fec_stats: the _fec calls with records, the
+        entries made and refused, and the member bytes XORed."""
+        st = N.FanoutFecStats()
+        N.check(N.lib().srtp_engine_fanout_fec_stats(self.h, C.byref(st)), self.h, "fanout_fec_stats")
+        return st.as_dict()
 
     def fanout_red_stats(self) -> dict:
         """srtp_engine_fanout_red_stats: the _red calls with records, and the
@@ -1782,6 +1892,96 @@ def fan_out_red(pkts: Sequence[Optional[RawPacket]], transformers: Sequence[_SRT
     return _fan_out(pkts, transformers, rewriters, exclusion, stampers, payload=True, payers=payers, reds=reds)
 
 
+class FecSender:
+    """FECSender's state for one SSRC toward one peer (transform/fec/
+    FECSender.java): ``counter`` media packets seen and ``nb_fec`` ulpfec
+    packets made, kept across :func:`fan_out_fec` calls; ``rate`` media packets
+    to a group (1..16, FECTransformEngine.java:236), ``pt`` the ulpfec payload
+    type and ``red_pt`` the RED payload type the packet is wrapped in (None:
+    sent plain)."""
+
+    def __init__(self, ssrc: int, rate: int, pt: int, red_pt: Optional[int] = None):
+        if not 1 <= int(rate) <= 16:
+            raise ValueError("FecSender: a rate of %r" % (rate,))
+        if not 0 <= int(pt) <= 127 or (red_pt is not None and not 0 <= int(red_pt) <= 127):
+            raise ValueError("FecSender: a payload type above 127")
+        self.ssrc, self.rate, self.pt = int(ssrc) & 0xFFFFFFFF, int(rate), int(pt)
+        self.red_pt = None if red_pt is None else int(red_pt)
+        self.counter = 0
+        self.nb_fec = 0
+
+
+def fan_out_fec(pkts: Sequence[Optional[RawPacket]], transformers: Sequence[_SRTPBase], rewriters, stampers, payers,
+                reds, fecs, exclusion=None):
+    """:func:`fan_out_red` for peers whose downlink is protected with ulpfec
+    (RFC 5109).  ``fecs`` holds one :class:`FecSender` (or None) per
+    transformer.  Every version-2 copy toward that transformer whose SSRC, as
+    its rewriter left it, is the sender's, is a media packet of the sender: its
+    (rewritten) sequence number is shifted by ``nb_fec``
+    (FECSender.transformSingle's ``setSequenceNumber(seq + nbFec)``, :132), and
+    after every ``rate`` of them an FEC entry follows, made on the GPU
+    (srtp_fanout_host_fec, one call) from the copies as all their records left
+    them -- FECSender.FECPacket's addMedia and finish (:319-412) over the
+    packets the peer gets -- and protected behind them in the same context
+    order.  A group still open at the end of the call is closed short; nothing
+    is carried between calls but ``counter`` and ``nb_fec``.
+
+    The ``fec`` key of a payer or rewriter keeps its meaning: it patches the SN
+    base of an FEC packet that came from elsewhere (:func:`fan_out_pay`); it
+    makes none.
+
+    Returns ``(out, codes, fec)``: ``out`` and ``codes`` as
+    :func:`fan_out_red`'s, ``fec[k]`` a list of ``(i, RawPacket or None)``: the
+    FEC packet sent toward transformer k behind packet i (None where it was
+    refused or not protected)."""
+    transformers, rewriters, stampers = list(transformers), list(rewriters), list(stampers)
+    payers, reds, fecs = list(payers), list(reds), list(fecs)
+    for name, x in (("rewriter", rewriters), ("stamper", stampers), ("payer", payers), ("(mode, red_pt)", reds),
+                    ("FecSender", fecs)):
+        if len(x) != len(transformers):
+            raise ValueError("fan_out_fec: one %s (or None) per transformer" % name)
+    for x in reds:
+        if x is not None and not (int(x[0]) in (RED_OFF, RED_STRIP, RED_WRAP) and 0 <= int(x[1]) <= 127):
+            raise ValueError("fan_out_fec: a RED record of %r" % (x,))
+    return _fan_out(pkts, transformers, rewriters, exclusion, stampers, payload=True, payers=payers, reds=reds,
+                    fecs=fecs)
+
+
+def _fec_entries(pkts, T, flags, rewrite, fecs):
+    """The FEC entries of one call: per transformer k with a sender, its media
+    entries in order, their sequence numbers shifted in ``rewrite`` (made where
+    it is None), a group closed after every ``rate``.  Returns ``(rewrite,
+    groups)``, ``groups`` a list of ``(k, i_last, [entry indices])``."""
+    groups = []
+    for k, snd in enumerate(fecs):
+        if snd is None:
+            continue
+        open_group = []
+        for i, p in enumerate(pkts):
+            j = i * T + k
+            if p is None or flags[j] & N.PKT_FLAG_SKIP or p.length < 12 or (p.readByte(0) >> 6) != 2:
+                continue
+            rw_on = rewrite is not None
+            ssrc = int(rewrite["ssrc"][j]) if rw_on and rewrite["mask"][j] & N.REWRITE_SSRC else p.getSSRC() & 0xFFFFFFFF
+            if ssrc != snd.ssrc:
+                continue
+            if rewrite is None:
+                rewrite = np.zeros(len(pkts) * T, N.FANOUT_REWRITE_DTYPE)
+            seq = int(rewrite["seq"][j]) if rewrite["mask"][j] & N.REWRITE_SEQ else p.getSequenceNumber()
+            rewrite["seq"][j] = (seq + snd.nb_fec) & 0xFFFF
+            rewrite["mask"][j] |= N.REWRITE_SEQ
+            snd.counter += 1
+            open_group.append(j)
+            if len(open_group) == snd.rate:
+                groups.append((k, i, open_group))
+                open_group = []
+                snd.nb_fec += 1
+        if open_group:  # closed short: nothing is carried between calls
+            groups.append((k, open_group[-1] // T, open_group))
+            snd.nb_fec += 1
+    return rewrite, groups
+
+
 def _pay_one(pay, j, r, p):
     """Entry j's payload record from the rewriter's mapping r: fec is patch 0, osn patch 1."""
     if "fec" in r:
@@ -1813,11 +2013,13 @@ def _stamp_one(stamp, j, g, p):
     stamp["id"][j], stamp["value"][j], stamp["on"][j] = int(ext_id), int(value) & 0x00FFFFFF, 1
 
 
-def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None, payload=False, payers=None, reds=None):
+def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None, payload=False, payers=None, reds=None,
+             fecs=None):
     pkts, transformers = list(pkts), list(transformers)
     out = [[None] * len(pkts) for _ in transformers]
     if not pkts or not transformers:
-        return out if reds is None else (out, [[0] * len(pkts) for _ in transformers])
+        codes = [[0] * len(pkts) for _ in transformers]
+        return out if reds is None else (out, codes) if fecs is None else (out, codes, [[] for _ in transformers])
     eng = transformers[0].engine
     if not isinstance(eng, SRTPEngine) or any(t.engine is not eng for t in transformers):
         raise ValueError("fan_out: the transformers of one SRTPEngine")
@@ -1884,6 +2086,26 @@ def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None, payload=Fa
                 if set(y) - {"osn", "fec"}:
                     raise ValueError("fan_out_red: a payer returned %s" % sorted(set(y) - {"osn", "fec"}))
                 _pay_one(pay, j, y, p)
+    n0, fec, members, groups = len(pkts) * T, None, None, []
+    if fecs is not None:
+        rewrite, groups = _fec_entries(pkts, T, flags, rewrite, fecs)
+    if groups:  # the FEC entries stand behind the media entries: no source, the peer's transformer, room for
+        g = len(groups)  # the 26 (27) header bytes less the 12 that are no payload
+        grow = lambda a, dt: None if a is None else np.concatenate((a, np.zeros(g, dt)))
+        rewrite, stamp, pay = (grow(rewrite, N.FANOUT_REWRITE_DTYPE), grow(stamp, N.FANOUT_AST_DTYPE),
+                               grow(pay, N.FANOUT_PAYLOAD_DTYPE))
+        fec = np.zeros(n0 + g, N.FANOUT_FEC_DTYPE)
+        members = np.array([j for _, _, js in groups for j in js], np.int32)
+        first = 0
+        for x, (k, _, js) in enumerate(groups):
+            snd = fecs[k]
+            fec[n0 + x] = (first, snd.ssrc, len(js), snd.pt, snd.red_pt or 0,
+                           N.FEC_PLAIN if snd.red_pt is None else N.FEC_RED)
+            first += len(js)
+        cap = np.concatenate((cap, [int(cap[js].max()) + 15 for _, _, js in groups])).astype(np.uint32)
+        src_idx = np.concatenate((src_idx, np.full(g, -1, np.int32)))
+        tids = np.concatenate((tids, [transformers[k].tid for k, _, _ in groups])).astype(np.int32)
+        flags = np.concatenate((flags, np.zeros(g, np.uint32)))
     step = (cap.astype(np.int64) + 15) & ~15
     off = np.concatenate(([0], np.cumsum(step)[:-1])).astype(np.int64)
     if int(off[-1] + step[-1]) >= 1 << 32:
@@ -1892,7 +2114,18 @@ def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None, payload=Fa
     if pay is not None and not (pay["at0"].any() or pay["at1"].any()):
         pay = None  # no rewriter named a payload value: fan_out_ast's call
     codes = None
-    if reds is None:
+    if fecs is not None:
+        red = None
+        if any(x is not None and int(x[0]) != RED_OFF for x in reds):
+            red = np.zeros(len(cap), N.FANOUT_RED_DTYPE)
+            for k, x in enumerate(reds):
+                if x is not None:
+                    red["mode"][k:n0:T], red["red_pt"][k:n0:T] = int(x[0]), int(x[1])
+        ln, st, ro, fo = eng.fanout_host_fec(tids, src_seg, src_off, src_len, src_cap, src_idx, seg,
+                                             off.astype(np.uint32), cap, src_status, flags, rewrite, stamp, pay, red,
+                                             fec, members)
+        codes = [[int(ro[i * T + k]) for i in range(len(pkts))] for k in range(T)]
+    elif reds is None:
         ln, st = eng.fanout_host_pay(tids, src_seg, src_off, src_len, src_cap, src_idx, seg, off.astype(np.uint32),
                                      cap, src_status, flags, rewrite, stamp, pay)
     else:
@@ -1905,10 +2138,17 @@ def _fan_out(pkts, transformers, rewriters, exclusion, stampers=None, payload=Fa
         ln, st, ro = eng.fanout_host_red(tids, src_seg, src_off, src_len, src_cap, src_idx, seg,
                                          off.astype(np.uint32), cap, src_status, flags, rewrite, stamp, pay, red)
         codes = [[int(ro[i * T + k]) for i in range(len(pkts))] for k in range(T)]
-    for j in np.nonzero(st == N.STATUS_OK)[0]:
+    for j in np.nonzero(st[:n0] == N.STATUS_OK)[0]:
         i, k = divmod(int(j), T)
         o = int(off[j])
         out[k][i] = RawPacket(seg[o:o + int(ln[j])].tobytes(), 0, int(ln[j]), pkts[i].flags)
+    if fecs is not None:
+        made = [[] for _ in transformers]
+        for x, (k, i, _) in enumerate(groups):
+            j, o = n0 + x, int(off[n0 + x])
+            ok = st[j] == N.STATUS_OK and fo[j] == N.FEC_MADE
+            made[k].append((i, RawPacket(seg[o:o + int(ln[j])].tobytes(), 0, int(ln[j]), 0) if ok else None))
+        return out, codes, made
     return out if reds is None else (out, codes)
 
 
