@@ -683,6 +683,85 @@ int srtp_engine_fanout_fec_stats(srtp_engine *e, srtp_fanout_fec_stats *out);
 int srtp_fanout_fec_job(const srtp_fanout_fec *rec, const uint8_t *bytes, const uint32_t *at, const uint32_t *lens,
                         uint8_t *out, uint32_t out_cap, int32_t *len_out, int8_t *code);
 
+/* Recovery of lost media packets from ulpfec (RFC 5109, one level, short or
+ * long mask) on the device: the receive half of the FEC engine, FECReceiver's
+ * Reconstructor (transform/fec/FECReceiver.java, setFecPacket :472-520 and
+ * recover :527-596), over the tables of a bundle that has been unprotected.
+ * The operation is stateless: record r names one FEC entry (`fec`) and up to 64
+ * candidate entries cand[first .. first + count) of the same tables -- the
+ * entries that may be its media packets, which the host can name from the clear
+ * RTP headers before the unprotect has run -- and the receiver's SSRC.  An
+ * entry, the FEC packet or a candidate, counts iff its index lies in [0, n),
+ * status[i] is SRTP_STATUS_OK (status == NULL: every entry) and 12 <= len[i] <=
+ * cap[i] <= 65535; a candidate that does not count is absent (a packet that
+ * failed authentication was not received).  Of candidates with equal sequence
+ * numbers the one latest in the list stands.  fec_rx_job.h states the rule line
+ * by line, with the reference's quirk kept (a key base + k above 65535 is never
+ * found) and the defined deviations (a read at or past the FEC packet's len
+ * refuses the record).  code[r]:
+ *   SRTP_FECRX_OFF        on == 0: nothing else of the record is read
+ *   SRTP_FECRX_RECOVERED  exactly one protected packet was missing; it is made
+ *   SRTP_FECRX_COMPLETE   none was missing: the FEC packet is of no further use
+ *   SRTP_FECRX_WAIT       more than one is missing
+ *   SRTP_FECRX_PARTIAL    protectionLength < lengthRecovery: the reference
+ *                         logs and returns null
+ *   SRTP_FECRX_REFUSED    count > 64, first + count > n_cand, the FEC entry
+ *                         does not count, or its header or payload does not lie
+ *                         below its len
+ * Recovered: out_len[r] = the packet's length, out_status[r] = SRTP_STATUS_OK
+ * and the bytes stand at out_seg + out_off[r]; a packet longer than out_cap[r]
+ * keeps its length, ends SRTP_STATUS_DROP_INVALID and only the pieces below
+ * out_cap[r] rounded up to 16 are stored.  Any other code: out_len[r] = 0,
+ * out_status[r] = SRTP_STATUS_SKIPPED and no byte of out_seg is written.  The
+ * arrays out_seg, out_off, out_len, out_cap and out_status are what
+ * srtp_fanout_device* takes as sources.  The input segment is never written;
+ * bytes of an output region at or past out_len[r] are unspecified.
+ *
+ * Device route: every array is device memory, rec and cand 4-byte aligned
+ * (else SRTP_EINVAL before any launch); asynchronous on `stream`; status and
+ * len are read on the device, so the arrays of a srtp_transform_device(reverse
+ * = 1) enqueued before on the same stream feed it with no synchronise.  Nothing
+ * is read back, no engine scratch is touched and no other stream's bundle is
+ * waited for.  Host route: both region tables are validated, a record or
+ * candidate index the rule would refuse is SRTP_EINVAL with nothing launched,
+ * and out_len, out_status, code and the output segment are copied back. */
+typedef struct { int32_t fec; uint32_t first, ssrc; uint8_t count, on; uint16_t reserved; } srtp_fec_recover;
+#define SRTP_FECRX_OFF 0
+#define SRTP_FECRX_RECOVERED 1
+#define SRTP_FECRX_COMPLETE 2
+#define SRTP_FECRX_WAIT 3
+#define SRTP_FECRX_PARTIAL 4
+#define SRTP_FECRX_REFUSED (-1)
+int srtp_fec_recover_device(srtp_engine *e, const uint8_t *seg, const uint32_t *off, const uint32_t *len,
+                            const uint32_t *cap, const int32_t *status, uint32_t n, const srtp_fec_recover *rec,
+                            uint32_t n_rec, const int32_t *cand, uint32_t n_cand, uint8_t *out_seg,
+                            const uint32_t *out_off, const uint32_t *out_cap, uint32_t *out_len, int32_t *out_status,
+                            int8_t *code, void *stream);
+int srtp_fec_recover_host(srtp_engine *e, const uint8_t *seg, size_t seg_bytes, const uint32_t *off,
+                          const uint32_t *len, const uint32_t *cap, const int32_t *status, uint32_t n,
+                          const srtp_fec_recover *rec, uint32_t n_rec, const int32_t *cand, uint32_t n_cand,
+                          uint8_t *out_seg, size_t out_seg_bytes, const uint32_t *out_off, const uint32_t *out_cap,
+                          uint32_t *out_len, int32_t *out_status, int8_t *code);
+/* Counters of the recover calls, cumulative since engine creation: the calls,
+ * and, counted by the kernel, the records that were on, how they ended, and the
+ * member bytes XORed (len - 4 per needed member of a recovered record).  The
+ * kernel's counts are those of the calls that have completed: synchronise the
+ * streams of the device route first. */
+typedef struct {
+    uint64_t calls, records, recovered, complete, waiting, partial, refused, member_bytes;
+} srtp_fec_recover_stats;
+int srtp_engine_fec_recover_stats(srtp_engine *e, srtp_fec_recover_stats *out);
+/* The recovery rule of one record (host only; fec_rx_job.h, the text
+ * k_fec_recover compiles): the FEC packet is fec[0 .. fec_len), candidate i is
+ * bytes[at[i] .. at[i] + lens[i]), i < rec->count, each with status OK and cap =
+ * its length; rec->fec and rec->first are not read.  *code gets the
+ * SRTP_FECRX_* code, *len_out the packet's length (0 unless recovered) and
+ * out[0 .. min(*len_out, out_cap)) its bytes, built piece by piece as the
+ * kernel builds them. */
+int srtp_fec_recover_job(const srtp_fec_recover *rec, const uint8_t *fec, uint32_t fec_len, const uint8_t *bytes,
+                         const uint32_t *at, const uint32_t *lens, uint8_t *out, uint32_t out_cap, int32_t *len_out,
+                         int8_t *code);
+
 /* The engine's own non-blocking stream, created with the engine so that each
  * engine gets a hardware queue of its own (streams created later may share
  * one, which serialises them): srtp_transform_host and the pipeline run their

@@ -11,9 +11,9 @@ from .srtp import (PacketTransformer, RawPacket, SRTCPTransformer, SRTPAggregato
                    SRTPEngine, SRTPPipeline, SRTPPolicy, SRTPTransformer, SRTPTransformException, pack,
                    HostBuffer, host_is_registered, host_register, host_unregister, profile_policies, transform_bundle,
                    fan_out, fan_out_rw, fan_out_ast, abs_send_time, fan_out_pay, fec_sn_bytes, reverse_transform_levels,
-                   fan_out_red, RED_OFF, RED_STRIP, RED_WRAP, fan_out_fec, FecSender)
+                   fan_out_red, RED_OFF, RED_STRIP, RED_WRAP, fan_out_fec, FecSender, FecReceiver)
 from . import _native  # noqa: F401
 
 __all__ = ["PacketTransformer", "RawPacket", "SRTCPTransformer", "SRTPAggregator", "SRTPContextFactory", "SRTPDispatcher", "SRTPEngine",
            "SRTPPipeline", "SRTPPolicy", "SRTPTransformer", "SRTPTransformException", "pack", "profile_policies",
-           "transform_bundle", "fan_out", "fan_out_rw", "fan_out_ast", "abs_send_time", "fan_out_pay", "fan_out_red", "fan_out_fec", "FecSender", "RED_OFF", "RED_STRIP", "RED_WRAP", "fec_sn_bytes", "reverse_transform_levels", "host_register", "host_unregister", "host_is_registered", "HostBuffer"]
+           "transform_bundle", "fan_out", "fan_out_rw", "fan_out_ast", "abs_send_time", "fan_out_pay", "fan_out_red", "fan_out_fec", "FecSender", "FecReceiver", "RED_OFF", "RED_STRIP", "RED_WRAP", "fec_sn_bytes", "reverse_transform_levels", "host_register", "host_unregister", "host_is_registered", "HostBuffer"]

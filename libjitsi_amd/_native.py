@@ -98,6 +98,7 @@ EXPORTED = [
     "srtp_audio_level_job",
     "srtp_fanout_device_red", "srtp_fanout_host_red", "srtp_engine_fanout_red_stats", "srtp_fanout_red_job",
     "srtp_fanout_device_fec", "srtp_fanout_host_fec", "srtp_engine_fanout_fec_stats", "srtp_fanout_fec_job",
+    "srtp_fec_recover_device", "srtp_fec_recover_host", "srtp_engine_fec_recover_stats", "srtp_fec_recover_job",
 ]
 STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 
@@ -105,7 +106,8 @@ STAGES = ["parse", "sort", "verify", "walk", "protect", "decrypt"]
 # Sources that decide what the crypto kernels execute: the key that ties
 # committed PMC counters (profiles/pmc_traffic.json) to the build they measured.
 KERNEL_SOURCES = ["srtp_kernels.hip", "aes_rounds_asm.inc", "srtp_kernels.h", "srtp_types.h", "engine.cpp",
-                  "gcm_job.h", "fanout_job.h", "bundle_plan.h", "audio_level_job.h", "red_job.h", "fec_job.h"]
+                  "gcm_job.h", "fanout_job.h", "bundle_plan.h", "audio_level_job.h", "red_job.h", "fec_job.h",
+                  "fec_rx_job.h"]
 
 
 def kernel_source_sha16() -> str:
@@ -274,6 +276,29 @@ FEC_NONE, FEC_MADE, FEC_REFUSED = 0, 1, -1  # fec_out
 class FanoutFecStats(C.Structure):
     """srtp_fanout_fec_stats (include/srtp_mi355x.h)"""
     _fields_ = [(n, C.c_uint64) for n in ("calls", "made", "refused", "member_bytes")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class FecRecover(C.Structure):
+    """srtp_fec_recover (include/srtp_mi355x.h): one recovery record"""
+    _fields_ = [("fec", C.c_int32), ("first", C.c_uint32), ("ssrc", C.c_uint32), ("count", C.c_uint8),
+                ("on", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+# numpy's view of an array of srtp_fec_recover (fec_recover_host)
+FEC_RECOVER_DTYPE = np.dtype([("fec", "<i4"), ("first", "<u4"), ("ssrc", "<u4"), ("count", "u1"), ("on", "u1"),
+                              ("reserved", "<u2")])
+# code[r] of a recovery
+FECRX_OFF, FECRX_RECOVERED, FECRX_COMPLETE, FECRX_WAIT, FECRX_PARTIAL, FECRX_REFUSED = 0, 1, 2, 3, 4, -1
+FECRX_MAX_CANDIDATES = 64  # FECReceiver.MEDIA_BUF_SIZE
+
+
+class FecRecoverStats(C.Structure):
+    """srtp_fec_recover_stats (include/srtp_mi355x.h)"""
+    _fields_ = [(n, C.c_uint64) for n in ("calls", "records", "recovered", "complete", "waiting", "partial",
+                                          "refused", "member_bytes")]
 
     def as_dict(self) -> dict:
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
@@ -464,6 +489,12 @@ def lib() -> C.CDLL:
     L.srtp_fanout_fec_job.argtypes = [C.POINTER(FanoutFec), vp, vp, vp, vp, u32, C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int8)]
     L.srtp_engine_fanout_fec_stats.argtypes = [vp, C.POINTER(FanoutFecStats)]
+    L.srtp_fec_recover_device.argtypes = [vp, vp, vp, vp, vp, vp, u32, vp, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    L.srtp_fec_recover_host.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, u32, vp, u32, vp, u32, vp, C.c_size_t,
+                                        vp, vp, vp, vp, vp]
+    L.srtp_fec_recover_job.argtypes = [C.POINTER(FecRecover), vp, u32, vp, vp, vp, vp, u32, C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int8)]
+    L.srtp_engine_fec_recover_stats.argtypes = [vp, C.POINTER(FecRecoverStats)]
     L.srtp_engine_fanout_stats.argtypes = [vp, C.POINTER(FanoutStats)]
     L.srtp_fanout_job.argtypes = [i32, i32, i32, i32, i32, i32, u32, C.POINTER(FanoutPlan)]
     L.srtp_transform_device_lvl.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, C.c_uint8, vp, vp, u32, vp]

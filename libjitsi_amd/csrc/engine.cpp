@@ -23,6 +23,7 @@
 #include "fanout_job.h"
 #include "red_job.h"
 #include "fec_job.h"
+#include "fec_rx_job.h"
 #include "gcm_job.h"
 #include "host_crypto.h"
 #include "srtp_kernels.h"
@@ -132,6 +133,14 @@ struct srtp_engine {
     uint32_t hs_fec_n = 0, hs_members_n = 0;
     unsigned long long *d_fec_stats = nullptr; // k_fanout_fec's rows: made, refused, member bytes, on-entries skipped
     uint64_t fec_calls = 0;
+    // FEC recovery (srtp_fec_recover_*): k_fec_recover's rows (recovered, complete, waiting, partial, refused,
+    // member bytes), published once they are zeroed, and the host route's records, candidates and codes
+    std::atomic<unsigned long long *> d_frx_stats{nullptr};
+    std::atomic<uint64_t> frx_calls{0};
+    srtp_fec_recover *hs_frx = nullptr;
+    int8_t *hs_frx_code = nullptr;
+    int32_t *hs_frx_cand = nullptr;
+    uint32_t hs_frx_n = 0, hs_frx_cand_n = 0;
     uint32_t *hs_off = nullptr, *hs_len = nullptr, *hs_cap = nullptr;
     int32_t *hs_status = nullptr, *hs_idx = nullptr;
     uint64_t fan_calls = 0, fan_sources = 0, fan_destinations = 0, fan_src_bytes = 0;
@@ -644,7 +653,8 @@ void srtp_engine_destroy(srtp_engine *e) {
                     e->h_cap, e->h_flags, e->h_status, e->h_tids, e->fan_flags, e->d_fan_skipped, e->hs_seg,
                     e->hs_off, e->hs_len, e->hs_cap, e->hs_status, e->hs_idx, e->hs_rw, e->hs_ast, e->hs_pay,
                     e->hs_red, e->hs_red_out, e->d_red_stats, e->hs_fec, e->hs_fec_out, e->hs_members,
-                    e->d_fec_stats, e->lvl_flags, e->d_lvl_stats, e->h_ext_ids, e->h_level};
+                    e->d_fec_stats, e->lvl_flags, e->d_lvl_stats, e->h_ext_ids, e->h_level, e->d_frx_stats.load(),
+                    e->hs_frx, e->hs_frx_code, e->hs_frx_cand};
     for (void *p : ptrs) dfree(p);
     if (e->ev_last) (void)hipEventDestroy(e->ev_last);
     if (e->ev_dev) (void)hipEventDestroy(e->ev_dev);
@@ -1621,6 +1631,247 @@ int srtp_fanout_fec_job(const srtp_fanout_fec *rec, const uint8_t *bytes, const 
         const uint32_t w[4] = {o.w0, o.w1, o.w2, o.w3};
         for (int b = 0; b < 16; b++) // the caller's buffer ends at out_cap, not at a piece's end
             if ((uint32_t)(16 * q + b) < out_cap && 16 * q + b < *len_out) out[16 * q + b] = (uint8_t)(w[b / 4] >> (8 * (b % 4)));
+    }
+    return SRTP_OK;
+}
+
+// ------------------------------------------------------------- FEC recovery
+// k_fec_recover on `s`.  The call reads the caller's tables and writes the
+// caller's outputs: no engine scratch, so no bundle of another stream is waited
+// for, and the engine's lock is taken only to make the counter rows.
+static int frx_stats_rows(srtp_engine *e, hipStream_t s, bool locked, unsigned long long **rows) {
+    *rows = e->d_frx_stats.load(std::memory_order_acquire);
+    if (*rows) return SRTP_OK;
+    std::unique_lock<std::mutex> g(e->mu, std::defer_lock);
+    if (!locked) g.lock();
+    *rows = e->d_frx_stats.load(std::memory_order_acquire);
+    if (*rows) return SRTP_OK;
+    unsigned long long *p = nullptr;
+    HIPCHK(e, dalloc(&p, kFecRxStatReplicas * kFecRxStatStride));
+    // zeroed before another thread's call on another stream can see the rows
+    hipError_t err = hipMemsetAsync(p, 0, kFecRxStatReplicas * kFecRxStatStride * sizeof(unsigned long long), s);
+    if (err == hipSuccess) err = hipStreamSynchronize(s);
+    if (err != hipSuccess) {
+        dfree(p);
+        HIPCHK(e, err);
+    }
+    e->d_frx_stats.store(p, std::memory_order_release);
+    *rows = p;
+    return SRTP_OK;
+}
+
+static int frx_launch(srtp_engine *e, const uint8_t *seg, const uint32_t *off, const uint32_t *len,
+                      const uint32_t *cap, const int32_t *status, uint32_t n, const srtp_fec_recover *rec,
+                      uint32_t n_rec, const int32_t *cand, uint32_t n_cand, uint8_t *out_seg, const uint32_t *out_off,
+                      const uint32_t *out_cap, uint32_t *out_len, int32_t *out_status, int8_t *code, hipStream_t s,
+                      bool locked) {
+    static_assert(sizeof(srtp_fec_recover) == 16 && offsetof(srtp_fec_recover, first) == 4 &&
+                      offsetof(srtp_fec_recover, ssrc) == 8 && offsetof(srtp_fec_recover, count) == 12 &&
+                      offsetof(srtp_fec_recover, on) == 13 && offsetof(srtp_fec_recover, reserved) == 14,
+                  "k_fec_recover loads a record as four 32-bit words");
+    static_assert(SRTP_FECRX_OFF == kFecRxOff && SRTP_FECRX_RECOVERED == kFecRxRecovered &&
+                      SRTP_FECRX_COMPLETE == kFecRxComplete && SRTP_FECRX_WAIT == kFecRxWait &&
+                      SRTP_FECRX_PARTIAL == kFecRxPartial && SRTP_FECRX_REFUSED == kFecRxRefused &&
+                      SRTP_STATUS_OK == kFecRxStatusOk && SRTP_STATUS_DROP_INVALID == kFecRxStatusInvalid &&
+                      SRTP_STATUS_SKIPPED == kFecRxStatusSkipped,
+                  "fec_rx_job.h restates these constants");
+    unsigned long long *rows = nullptr;
+    int rc = frx_stats_rows(e, s, locked, &rows);
+    if (rc != SRTP_OK) return rc;
+    FecRecoverArgs a{};
+    a.seg = seg; a.off = off; a.len = len; a.cap = cap; a.status = status; a.n = n;
+    a.rec = reinterpret_cast<const uint32_t *>(rec); a.n_rec = n_rec;
+    a.cand = cand; a.n_cand = n_cand;
+    a.out_seg = out_seg; a.out_off = out_off; a.out_cap = out_cap; a.out_len = out_len;
+    a.out_status = out_status; a.code = code;
+    a.stats = rows;
+    HIPCHK(e, launch_fec_recover(a, s));
+    e->frx_calls.fetch_add(1, std::memory_order_relaxed);
+    return SRTP_OK;
+}
+
+// What both routes check of the arguments before anything else.  The message, or null.
+static const char *frx_refusal(const void *seg, const void *off, const void *len, const void *cap, uint32_t n,
+                               const void *rec, const void *cand, uint32_t n_cand, const void *out_seg,
+                               const void *out_off, const void *out_cap, const void *out_len, const void *out_status,
+                               const void *code) {
+    if (!seg || !off || !len || !cap || !rec || !out_seg || !out_off || !out_cap || !out_len || !out_status || !code)
+        return "null buffer";
+    if (n_cand && !cand) return "cand is NULL";
+    if (n == 0 || n > (uint32_t)INT32_MAX) return "recovery without an entry, or with too many";
+    return nullptr;
+}
+
+int srtp_fec_recover_device(srtp_engine *e, const uint8_t *seg, const uint32_t *off, const uint32_t *len,
+                            const uint32_t *cap, const int32_t *status, uint32_t n, const srtp_fec_recover *rec,
+                            uint32_t n_rec, const int32_t *cand, uint32_t n_cand, uint8_t *out_seg,
+                            const uint32_t *out_off, const uint32_t *out_cap, uint32_t *out_len, int32_t *out_status,
+                            int8_t *code, void *stream) {
+    if (!e) return SRTP_EINVAL;
+    if (n_rec == 0) return SRTP_OK;
+    // not under the lock: two threads that fail at once race for last_error alone, as they would for any call
+    if (const char *why = frx_refusal(seg, off, len, cap, n, rec, cand, n_cand, out_seg, out_off, out_cap, out_len,
+                                      out_status, code)) {
+        std::lock_guard<std::mutex> g(e->mu);
+        return fail(e, SRTP_EINVAL, why);
+    }
+    if (((uintptr_t)rec & 3u) || ((uintptr_t)cand & 3u)) { // k_fec_recover loads words
+        std::lock_guard<std::mutex> g(e->mu);
+        return fail(e, SRTP_EINVAL, "rec and cand must be 4-byte aligned");
+    }
+    GUARD(e);
+    return frx_launch(e, seg, off, len, cap, status, n, rec, n_rec, cand, n_cand, out_seg, out_off, out_cap, out_len,
+                      out_status, code, (hipStream_t)stream, false);
+}
+
+int srtp_fec_recover_host(srtp_engine *e, const uint8_t *seg, size_t seg_bytes, const uint32_t *off,
+                          const uint32_t *len, const uint32_t *cap, const int32_t *status, uint32_t n,
+                          const srtp_fec_recover *rec, uint32_t n_rec, const int32_t *cand, uint32_t n_cand,
+                          uint8_t *out_seg, size_t out_seg_bytes, const uint32_t *out_off, const uint32_t *out_cap,
+                          uint32_t *out_len, int32_t *out_status, int8_t *code) {
+    if (!e) return SRTP_EINVAL;
+    if (n_rec == 0) return SRTP_OK;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (const char *why = frx_refusal(seg, off, len, cap, n, rec, cand, n_cand, out_seg, out_off, out_cap, out_len,
+                                      out_status, code))
+        return fail(e, SRTP_EINVAL, why);
+    int rc = check_size(e, n);
+    if (rc == SRTP_OK) rc = check_size(e, n_rec);
+    if (rc == SRTP_OK) rc = validate_regions(e, off, cap, n, seg_bytes);
+    if (rc == SRTP_OK) rc = validate_regions(e, out_off, out_cap, n_rec, out_seg_bytes);
+    if (rc != SRTP_OK) return rc;
+    for (uint32_t r = 0; r < n_rec; r++) { // what the rule would refuse for the record's fields or indices
+        if (!rec[r].on) continue;
+        if (!fecrx_record_ok(rec[r].first, rec[r].count, n_cand))
+            return fail(e, SRTP_EINVAL, "rec[r] names more than 64 candidates, or candidates past n_cand");
+        if (!fecrx_index_ok(rec[r].fec, (int)n)) return fail(e, SRTP_EINVAL, "rec[r].fec names no entry");
+        for (uint32_t k = 0; k < rec[r].count; k++)
+            if (!fecrx_index_ok(cand[rec[r].first + k], (int)n))
+                return fail(e, SRTP_EINVAL, "a candidate names no entry");
+    }
+    GUARD(e);
+    hipStream_t s = e->stream;
+    rc = ensure_host_staging(e, out_seg_bytes, n_rec);
+    if (rc != SRTP_OK) return rc;
+    const size_t need = (seg_bytes + 15) & ~(size_t)15;
+    if ((need > e->hs_seg_bytes || n > e->hs_m || n_rec > e->hs_frx_n || n_cand > e->hs_frx_cand_n) && e->have_last) {
+        rc = quiesce(e); // the source staging may still be read by an enqueued fan-out
+        if (rc != SRTP_OK) return rc;
+    }
+    rc = grow_staging(e, &e->hs_seg_bytes, need, &e->hs_seg);
+    if (rc == SRTP_OK) rc = grow_staging(e, &e->hs_m, n, &e->hs_off, &e->hs_len, &e->hs_cap, &e->hs_status);
+    if (rc == SRTP_OK) rc = grow_staging(e, &e->hs_frx_n, n_rec, &e->hs_frx, &e->hs_frx_code);
+    if (rc == SRTP_OK) rc = grow_staging(e, &e->hs_frx_cand_n, std::max<uint32_t>(n_cand, 1), &e->hs_frx_cand);
+    if (rc != SRTP_OK) return rc;
+    // the staging is shared with the bundles' host routes: behind the last bundle of another stream
+    if (e->have_last && e->last_stream != s) HIPCHK(e, hipStreamWaitEvent(s, last_event(e), 0));
+    HIPCHK(e, hipMemcpyAsync(e->hs_seg, seg, seg_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->hs_off, off, n * 4ull, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->hs_len, len, n * 4ull, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->hs_cap, cap, n * 4ull, hipMemcpyHostToDevice, s));
+    if (status) HIPCHK(e, hipMemcpyAsync(e->hs_status, status, n * 4ull, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->hs_frx, rec, n_rec * sizeof *rec, hipMemcpyHostToDevice, s));
+    if (n_cand) HIPCHK(e, hipMemcpyAsync(e->hs_frx_cand, cand, n_cand * 4ull, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->h_seg, out_seg, out_seg_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->h_off, out_off, n_rec * 4ull, hipMemcpyHostToDevice, s));
+    HIPCHK(e, hipMemcpyAsync(e->h_cap, out_cap, n_rec * 4ull, hipMemcpyHostToDevice, s));
+    rc = frx_launch(e, e->hs_seg, e->hs_off, e->hs_len, e->hs_cap, status ? e->hs_status : nullptr, n, e->hs_frx,
+                    n_rec, e->hs_frx_cand, n_cand, e->h_seg, e->h_off, e->h_cap, e->h_len, e->h_status,
+                    e->hs_frx_code, s, true);
+    if (rc != SRTP_OK) return rc;
+    HIPCHK(e, hipMemcpyAsync(out_seg, e->h_seg, out_seg_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(out_len, e->h_len, n_rec * 4ull, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(out_status, e->h_status, n_rec * 4ull, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipMemcpyAsync(code, e->hs_frx_code, n_rec, hipMemcpyDeviceToHost, s));
+    HIPCHK(e, hipStreamSynchronize(s));
+    return SRTP_OK;
+}
+
+int srtp_engine_fec_recover_stats(srtp_engine *e, srtp_fec_recover_stats *out) {
+    if (!e || !out) return SRTP_EINVAL;
+    std::lock_guard<std::mutex> g(e->mu);
+    memset(out, 0, sizeof *out);
+    out->calls = e->frx_calls.load(std::memory_order_relaxed);
+    const unsigned long long *rows = e->d_frx_stats.load(std::memory_order_acquire);
+    if (!rows) return SRTP_OK; // no recover call yet
+    GUARD(e);
+    int rc = quiesce(e);
+    if (rc != SRTP_OK) return rc;
+    unsigned long long st[kFecRxStatReplicas * kFecRxStatStride];
+    HIPCHK(e, hipMemcpy(st, rows, sizeof st, hipMemcpyDeviceToHost));
+    for (uint32_t r = 0; r < kFecRxStatReplicas; r++) { // a row per group of waves (k_fec_recover)
+        out->recovered += st[r * kFecRxStatStride + 0];
+        out->complete += st[r * kFecRxStatStride + 1];
+        out->waiting += st[r * kFecRxStatStride + 2];
+        out->partial += st[r * kFecRxStatStride + 3];
+        out->refused += st[r * kFecRxStatStride + 4];
+        out->member_bytes += st[r * kFecRxStatStride + 5];
+    }
+    out->records = out->recovered + out->complete + out->waiting + out->partial + out->refused;
+    return SRTP_OK;
+}
+
+namespace {
+struct FecRxBytes { // the caller's FEC packet as fecrx_head reads it
+    const uint8_t *pkt;
+    int len;
+    int operator()(int i) const { return i >= 0 && i < len ? pkt[i] : 0; }
+};
+} // namespace
+
+int srtp_fec_recover_job(const srtp_fec_recover *rec, const uint8_t *fec, uint32_t fec_len, const uint8_t *bytes,
+                         const uint32_t *at, const uint32_t *lens, uint8_t *out, uint32_t out_cap, int32_t *len_out,
+                         int8_t *code) {
+    if (!rec || !len_out || !code) return SRTP_EINVAL;
+    *len_out = 0;
+    *code = SRTP_FECRX_OFF;
+    if (!rec->on) return SRTP_OK;
+    *code = SRTP_FECRX_REFUSED;
+    if (!fecrx_record_ok(0, rec->count, rec->count)) return SRTP_OK;
+    if (fec_len > (uint32_t)kFanMaxRegion || !fecrx_entry_ok(kFecRxStatusOk, (int)fec_len, (int)fec_len)) return SRTP_OK;
+    if (!fec || (rec->count && (!bytes || !at || !lens))) return SRTP_EINVAL;
+    const FecRxHead h = fecrx_head(FecRxBytes{fec, (int)fec_len}, (int)fec_len);
+    if (h.code != 0) return SRTP_OK;
+    // a word of an entry as the kernel loads it: bytes at or past len are whatever lies there (0xA5 here)
+    auto word = [](const uint8_t *p, int len, int w) {
+        uint32_t v = 0;
+        for (int b = 0; b < 4; b++) {
+            const int i = 4 * w + b;
+            v |= (uint32_t)(i < len ? p[i] : 0xA5u) << (8 * b);
+        }
+        return v;
+    };
+    auto present = [&](int k) { return lens[k] <= (uint32_t)kFanMaxRegion && fecrx_entry_ok(0, (int)lens[k], (int)lens[k]); };
+    uint64_t covered = 0, needed = 0;
+    int len_xor = 0;
+    for (int k = (int)rec->count - 1; k >= 0; k--) { // from the last candidate to the first
+        if (!present(k)) continue;
+        if (fecrx_take(covered, fecrx_bit(fecrx_key(word(bytes + at[k], (int)lens[k], 0)), h))) {
+            needed |= 1ull << k;
+            len_xor ^= (int)lens[k] - kFanHeaderBytes;
+        }
+    }
+    const FecRxPlan p = fecrx_plan(h, covered, len_xor, (int)fec_len);
+    *code = (int8_t)p.code;
+    *len_out = p.len_out;
+    if (p.code != kFecRxRecovered) return SRTP_OK;
+    const int store = fecrx_store_bytes(p.len_out, out_cap > (uint32_t)kFanMaxRegion ? kFanMaxRegion : (int)out_cap);
+    if (store && !out) return SRTP_EINVAL;
+    for (int q = 0; q < store / 16; q++) {
+        uint32_t F[5];
+        for (int i = 0; i < 5; i++) F[i] = word(fec, (int)fec_len, fecrx_fec_word(q, i, h, (int)fec_len));
+        FecRxWindow a{0, 0, 0, 0};
+        for (uint32_t k = 0; k < rec->count; k++) {
+            if (!((needed >> k) & 1ull)) continue;
+            const int len = (int)lens[k], sp = fecrx_src_piece(q, len);
+            const uint8_t *m = bytes + at[k];
+            fecrx_accumulate(a, FanoutPiece{word(m, len, 4 * sp), word(m, len, 4 * sp + 1), word(m, len, 4 * sp + 2),
+                                            word(m, len, 4 * sp + 3)}, q, len);
+        }
+        const FanoutPiece o = fecrx_piece(a, F[0], F[1], F[2], F[3], F[4], q, h, p, (int)fec_len, rec->ssrc);
+        const uint32_t w[4] = {o.w0, o.w1, o.w2, o.w3};
+        for (int b = 0; b < 16; b++) // the caller's buffer ends at out_cap, not at a piece's end
+            if ((uint32_t)(16 * q + b) < out_cap && 16 * q + b < p.len_out) out[16 * q + b] = (uint8_t)(w[b / 4] >> (8 * (b % 4)));
     }
     return SRTP_OK;
 }

@@ -224,6 +224,35 @@ struct FanFecArgs {
     unsigned long long *stats; // [kFecStatReplicas][kFecStatStride]
 };
 hipError_t launch_fanout_fec(const FanoutArgs &f, const FanFecArgs &x, hipStream_t s);
+// srtp_fec_recover_*: behind an unprotect, a wave per record gives back the
+// media packet that record r's ulpfec entry and its candidates yield
+// (k_fec_recover, the rule in fec_rx_job.h).  seg, off, len, cap and status
+// (null: every entry OK) are the received tables, read only; rec: n_rec 16-byte
+// records (srtp_fec_recover as four words: fec, first, ssrc, count | on << 8 |
+// reserved << 16), 4-byte aligned; cand: n_cand entry indices, 4-byte aligned.
+// out_len[r], out_status[r] and code[r] are written for every record, out_seg
+// inside the regions of recovered records only.  stats: kFecRxStatReplicas rows
+// of kFecRxStatStride words (64 bytes): a wave adds its records recovered,
+// complete, waiting, partial and refused and the member bytes it XORed to words
+// 0..5 of one row, and the host sums the rows.
+constexpr uint32_t kFecRxStatReplicas = 64, kFecRxStatStride = 8;
+struct FecRecoverArgs {
+    const uint8_t *seg;
+    const uint32_t *off, *len, *cap; // [n]
+    const int32_t *status;           // [n] may be null
+    uint32_t n;                      // <= INT32_MAX
+    const uint32_t *rec;             // [4 n_rec]
+    uint32_t n_rec;
+    const int32_t *cand;             // [n_cand]
+    uint32_t n_cand;
+    uint8_t *out_seg;
+    const uint32_t *out_off, *out_cap; // [n_rec]
+    uint32_t *out_len;                 // [n_rec] out
+    int32_t *out_status;               // [n_rec] out
+    int8_t *code;                      // [n_rec] out
+    unsigned long long *stats;         // [kFecRxStatReplicas][kFecRxStatStride]
+};
+hipError_t launch_fec_recover(const FecRecoverArgs &a, hipStream_t s);
 // srtp_transform_device_lvl: in front of the unprotect chain, entry j's
 // ssrc-audio-level is read and its flags word made (k_audio_level, the rule in
 // audio_level_job.h): level[j] = the level (0..127) or -128, flags_out[j] =

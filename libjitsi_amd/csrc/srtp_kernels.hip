@@ -66,6 +66,7 @@
 #include "audio_level_job.h"
 #include "fanout_job.h"
 #include "fec_job.h"
+#include "fec_rx_job.h"
 #include "gcm_job.h"
 #include "red_job.h"
 #include "srtp_kernels.h"
@@ -7865,6 +7866,169 @@ hipError_t launch_fanout_fec(const FanoutArgs &f, const FanFecArgs &x, hipStream
     if (f.n == 0) return hipSuccess;
     const uint32_t wgs = std::min<uint32_t>((f.n + 3u) / 4u, 4096u); // an entry per wave
     hipLaunchKernelGGL(k_fanout_fec, dim3(wgs), dim3(kGatherBlock), 0, s, f, x);
+    return hipGetLastError();
+}
+
+// FEC recovery (k_fec_recover, srtp_fec_recover_*): behind an unprotect, a wave
+// per record.  A record that is off costs its wave one scalar load.  For a
+// record that is on, fecrx_record_ok is asked with the record and n_cand alone;
+// the FEC entry's index, then its status, len and cap, then its header
+// (fecrx_head through a reader of wave-uniform byte loads below len) are the
+// wave's; lanes 0 .. count - 1 each take one candidate: its index, and only
+// where that lies in [0, n) its status, len and cap, and only where
+// fecrx_entry_ok passes on those (12 <= len <= cap: the region owns its first 16
+// bytes) its first word.  The candidates that stand for a mask bit are taken off
+// a ballot from the last to the first (fecrx_take: the later of two equal keys
+// stands), which gives the needed set, the covered mask and the XOR of the
+// lengths as wave-uniform values; fecrx_plan gives the verdict, the same in
+// every lane, before any pointer into either segment beyond the headers is
+// formed.  A record that does not recover forms no pointer into out_seg.
+//
+// Then lanes stride over the packet's 16-byte pieces.  Piece q takes of each
+// needed member the aligned piece fecrx_src_piece names (piece 0, masked, where
+// the member ends before it), four members to a batch -- a batch's loads stand
+// before its first XOR -- and of the FEC packet the five aligned words
+// fecrx_fec_word names, funnelled once (fecrx_piece; piece 0 takes the header).
+//
+// Bounds.  loads: words and pieces that start below an entry's len, hence below
+// len rounded up to 16, at most its cap rounded up to 16.  stores: pieces below
+// fecrx_store_bytes = min(len_out, out_cap[r]) rounded up to 16 of record r's own
+// output region, and out_len[r], out_status[r], code[r].  The input segment is
+// only read.
+struct FecRxReader {
+    const uint8_t *pkt; // the FEC entry's region; the rule asks below len only
+    __device__ __forceinline__ int operator()(int i) const { return __builtin_amdgcn_readfirstlane((int)pkt[i]); }
+};
+
+__global__ __launch_bounds__(kGatherBlock) void k_fec_recover(FecRecoverArgs a) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (kGatherBlock / 64) + (threadIdx.x >> 6));
+    const uint32_t waves = gridDim.x * (kGatherBlock / 64);
+    uint32_t n_rcv = 0u, n_cpl = 0u, n_wait = 0u, n_part = 0u, n_ref = 0u; // the wave's, the same in every lane
+    unsigned long long n_bytes = 0ull;
+    for (uint32_t r = wave; r < a.n_rec; r += waves) {
+        const uint32_t r3 = __builtin_amdgcn_readfirstlane(a.rec[4u * r + 3u]);
+        if (((r3 >> 8) & 0xFFu) == 0u) {
+            if (lane == 0u) {
+                a.out_len[r] = 0u;
+                a.out_status[r] = kFecRxStatusSkipped;
+                a.code[r] = (int8_t)kFecRxOff;
+            }
+            continue;
+        }
+        const int fi = (int)__builtin_amdgcn_readfirstlane(a.rec[4u * r]);
+        const uint32_t first = __builtin_amdgcn_readfirstlane(a.rec[4u * r + 1u]);
+        const uint32_t ssrc = __builtin_amdgcn_readfirstlane(a.rec[4u * r + 2u]);
+        const uint32_t count = r3 & 0xFFu;
+        const bool rec_ok = fecrx_record_ok(first, count, a.n_cand);
+        FecRxHead h;
+        h.code = kFecRxRefused;
+        uint32_t foff = 0u;
+        int flen = 0;
+        if (rec_ok && fecrx_index_ok(fi, (int)a.n)) {
+            const int st = a.status ? __builtin_amdgcn_readfirstlane(a.status[fi]) : kFecRxStatusOk;
+            const int fl = (int)__builtin_amdgcn_readfirstlane(a.len[fi]);
+            const int fc = (int)__builtin_amdgcn_readfirstlane(a.cap[fi]);
+            if (fecrx_entry_ok(st, fl, fc)) {
+                foff = __builtin_amdgcn_readfirstlane(a.off[fi]);
+                flen = fl;
+                h = fecrx_head(FecRxReader{a.seg + foff}, fl);
+            }
+        }
+        FecRxPlan p;
+        p.code = kFecRxRefused;
+        p.key = 0;
+        p.lr = 0;
+        p.len_out = 0;
+        uint32_t coff = 0u;
+        int clen = 0;
+        unsigned long long needed = 0ull;
+        if (h.code == 0) { // the same in every lane
+            int d = -1;
+            if (lane < count) {
+                const int ci = a.cand[first + lane];
+                if (fecrx_index_ok(ci, (int)a.n)) {
+                    const int st = a.status ? a.status[ci] : kFecRxStatusOk;
+                    const int cl = (int)a.len[ci], cc = (int)a.cap[ci];
+                    if (fecrx_entry_ok(st, cl, cc)) {
+                        coff = a.off[ci];
+                        clen = cl;
+                        d = fecrx_bit(fecrx_key(*reinterpret_cast<const uint32_t *>(a.seg + coff)), h);
+                    }
+                }
+            }
+            unsigned long long hits = __ballot(d >= 0);
+            uint64_t covered = 0u;
+            int len_xor = 0;
+            while (hits) { // from the last candidate to the first
+                const int k = 63 - __builtin_clzll(hits);
+                hits &= ~(1ull << k);
+                if (fecrx_take(covered, __builtin_amdgcn_readlane(d, k))) {
+                    needed |= 1ull << k;
+                    len_xor ^= __builtin_amdgcn_readlane(clen, k) - kFanHeaderBytes;
+                }
+            }
+            p = fecrx_plan(h, covered, len_xor, flen);
+        }
+        const int ocap = (int)__builtin_amdgcn_readfirstlane(a.out_cap[r]);
+        if (lane == 0u) {
+            a.out_len[r] = (uint32_t)p.len_out;
+            a.out_status[r] = fecrx_status(p, ocap);
+            a.code[r] = (int8_t)p.code;
+        }
+        n_rcv += p.code == kFecRxRecovered ? 1u : 0u;
+        n_cpl += p.code == kFecRxComplete ? 1u : 0u;
+        n_wait += p.code == kFecRxWait ? 1u : 0u;
+        n_part += p.code == kFecRxPartial ? 1u : 0u;
+        n_ref += p.code == kFecRxRefused ? 1u : 0u;
+        if (p.code != kFecRxRecovered) continue;
+        for (unsigned long long m = needed; m; m &= m - 1ull)
+            n_bytes += (unsigned long long)(__builtin_amdgcn_readlane(clen, __builtin_ctzll(m)) - 4);
+        const uint32_t wd = (uint32_t)fecrx_store_bytes(p.len_out, ocap) / 16u;
+        if (wd == 0u) continue; // nothing to store: no destination pointer is formed
+        uint4 *t = reinterpret_cast<uint4 *>(a.out_seg + __builtin_amdgcn_readfirstlane(a.out_off[r]));
+        const uint32_t *fw = reinterpret_cast<const uint32_t *>(a.seg + foff);
+        for (uint32_t q = lane; q < wd; q += 64u) {
+            uint32_t F[5];
+#pragma unroll
+            for (int i = 0; i < 5; i++) F[i] = fw[fecrx_fec_word((int)q, i, h, flen)];
+            FecRxWindow w = {0u, 0u, 0u, 0u};
+            unsigned long long m = needed;
+            while (m) {
+                uint4 P[4];
+                int L[4];
+                int k = __builtin_ctzll(m);
+#pragma unroll
+                for (uint32_t i = 0u; i < 4u; i++) { // a slot past the last member reads the last one's piece 0, masked
+                    const uint8_t *mb = a.seg + (uint32_t)__builtin_amdgcn_readlane((int)coff, k);
+                    L[i] = m ? __builtin_amdgcn_readlane(clen, k) : 0;
+                    P[i] = reinterpret_cast<const uint4 *>(mb)[fecrx_src_piece((int)q, L[i])];
+                    m &= m - 1ull;
+                    k = m ? __builtin_ctzll(m) : k;
+                }
+#pragma unroll
+                for (uint32_t i = 0u; i < 4u; i++)
+                    fecrx_accumulate(w, FanoutPiece{P[i].x, P[i].y, P[i].z, P[i].w}, (int)q, L[i]);
+            }
+            const FanoutPiece o = fecrx_piece(w, F[0], F[1], F[2], F[3], F[4], (int)q, h, p, flen, ssrc);
+            t[q] = uint4{o.w0, o.w1, o.w2, o.w3};
+        }
+    }
+    if (lane == 0u) { // one of kFecRxStatReplicas rows, by wave, as k_audio_level's
+        unsigned long long *row = a.stats + kFecRxStatStride * (wave % kFecRxStatReplicas);
+        if (n_rcv) atomicAdd(row + 0, (unsigned long long)n_rcv);
+        if (n_cpl) atomicAdd(row + 1, (unsigned long long)n_cpl);
+        if (n_wait) atomicAdd(row + 2, (unsigned long long)n_wait);
+        if (n_part) atomicAdd(row + 3, (unsigned long long)n_part);
+        if (n_ref) atomicAdd(row + 4, (unsigned long long)n_ref);
+        if (n_bytes) atomicAdd(row + 5, n_bytes);
+    }
+}
+
+hipError_t launch_fec_recover(const FecRecoverArgs &a, hipStream_t s) {
+    if (a.n_rec == 0) return hipSuccess;
+    const uint32_t wgs = std::min<uint32_t>((a.n_rec + 3u) / 4u, 4096u); // a record per wave
+    hipLaunchKernelGGL(k_fec_recover, dim3(wgs), dim3(kGatherBlock), 0, s, a);
     return hipGetLastError();
 }
 

@@ -23,6 +23,7 @@ packs RawPackets into one bundle and unpacks the results.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 import threading
 from typing import List, Optional, Sequence
@@ -925,6 +926,80 @@ class SRTPEngine:
         entries made and refused, and the member bytes XORed."""
         st = N.FanoutFecStats()
         N.check(N.lib().srtp_engine_fanout_fec_stats(self.h, C.byref(st)), self.h, "fanout_fec_stats")
+        return st.as_dict()
+
+    def fec_recover_device(self, seg, off, length, cap, status, rec, cand, out_seg, out_off, out_cap, out_len,
+                           out_status, code, n: Optional[int] = None, n_rec: Optional[int] = None,
+                           n_cand: Optional[int] = None, stream=None) -> None:
+        """srtp_fec_recover_device: FECReceiver.Reconstructor (FECReceiver.java,
+        setFecPacket :472-520 and recover :527-596) over the tables of a bundle
+        that :meth:`transform_device` ``(reverse=True)`` has unprotected, on
+        ``stream`` and with nothing read back.  Every argument is a tensor on
+        this engine's GPU: ``rec`` holds n_rec x 16 bytes, 4-byte aligned
+        (records of ``N.FEC_RECOVER_DTYPE``: fec, first, ssrc, count, on), and
+        ``cand`` n_cand int32 entry indices; ``status`` may be None (every
+        entry OK).  Record r recovers the one packet its FEC entry protects
+        and ``cand[first .. first + count)`` lack, into ``out_seg`` at
+        ``out_off[r]``; ``code`` (int8) gets ``N.FECRX_*``, ``out_len`` and
+        ``out_status`` what :meth:`fanout_device` takes of a source."""
+        n = off.numel() if n is None else n
+        n_cand = (0 if cand is None else cand.numel()) if n_cand is None else n_cand
+        if n_rec is None:
+            n_rec = out_off.numel()
+        if rec.numel() * rec.element_size() < 16 * n_rec:
+            raise ValueError("fec_recover_device: rec holds fewer than n_rec records")
+        if cand is not None and cand.numel() * cand.element_size() < 4 * n_cand:
+            raise ValueError("fec_recover_device: cand holds fewer than n_cand indices")
+        if code.element_size() != 1 or code.numel() < n_rec:
+            raise ValueError("fec_recover_device: code holds fewer than n_rec 1-byte elements")
+        for name, t in (("out_cap", out_cap), ("out_len", out_len), ("out_status", out_status)):
+            if t.numel() * t.element_size() < 4 * n_rec:
+                raise ValueError("fec_recover_device: %s holds fewer than n_rec elements" % name)
+        sp = getattr(stream, "cuda_stream", stream)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        rc = N.lib().srtp_fec_recover_device(
+            self.h, seg.data_ptr(), off.data_ptr(), length.data_ptr(), cap.data_ptr(), ptr(status), n,
+            rec.data_ptr(), n_rec, ptr(cand), n_cand, out_seg.data_ptr(), out_off.data_ptr(), out_cap.data_ptr(),
+            out_len.data_ptr(), out_status.data_ptr(), code.data_ptr(), sp)
+        N.check(rc, self.h, "srtp_fec_recover_device")
+
+    def fec_recover_host(self, seg: np.ndarray, off, length, cap, rec, cand, out_seg: np.ndarray, out_off, out_cap,
+                         status=None):
+        """srtp_fec_recover_host over numpy: what :meth:`fec_recover_device`
+        does, with the tables staged to the device and ``out_seg`` and the
+        results copied back.  ``rec`` is a structured array of dtype
+        ``N.FEC_RECOVER_DTYPE``, ``cand`` an int32 array.  A record or candidate
+        index the rule would refuse raises (SRTP_EINVAL).  Returns ``(out_len,
+        out_status, code)``."""
+        assert seg.dtype == np.uint8 and seg.flags.c_contiguous
+        assert out_seg.dtype == np.uint8 and out_seg.flags.c_contiguous and out_seg.flags.writeable
+        off = np.ascontiguousarray(off, np.uint32)
+        length = np.ascontiguousarray(length, np.uint32)
+        cap = np.ascontiguousarray(cap, np.uint32)
+        out_off = np.ascontiguousarray(out_off, np.uint32)
+        out_cap = np.ascontiguousarray(out_cap, np.uint32)
+        rc_ = np.ascontiguousarray(rec, N.FEC_RECOVER_DTYPE)
+        cd = np.ascontiguousarray(np.zeros(0, np.int32) if cand is None else cand, np.int32)
+        st = None if status is None else np.ascontiguousarray(status, np.int32)
+        n, n_rec = len(off), len(rc_)
+        assert len(length) == n and len(cap) == n and (st is None or len(st) == n)
+        assert len(out_off) == n_rec and len(out_cap) == n_rec
+        out_len = np.zeros(n_rec, np.uint32)
+        out_status = np.zeros(n_rec, np.int32)
+        code = np.zeros(n_rec, np.int8)
+        rc = N.lib().srtp_fec_recover_host(
+            self.h, seg.ctypes.data, seg.nbytes, off.ctypes.data, length.ctypes.data, cap.ctypes.data,
+            None if st is None else st.ctypes.data, n, rc_.ctypes.data, n_rec, cd.ctypes.data if len(cd) else None,
+            len(cd), out_seg.ctypes.data, out_seg.nbytes, out_off.ctypes.data, out_cap.ctypes.data,
+            out_len.ctypes.data, out_status.ctypes.data, code.ctypes.data)
+        N.check(rc, self.h, "srtp_fec_recover_host")
+        return out_len, out_status, code
+
+    def fec_recover_stats(self) -> dict:
+        """srtp_engine_fec_recover_stats: the recover calls, the records that
+        were on and how they ended, and the member bytes XORed."""
+        st = N.FecRecoverStats()
+        N.check(N.lib().srtp_engine_fec_recover_stats(self.h, C.byref(st)), self.h, "fec_recover_stats")
         return st.as_dict()
 
     def fanout_red_stats(self) -> dict:
@@ -1945,6 +2020,128 @@ def fan_out_fec(pkts: Sequence[Optional[RawPacket]], transformers: Sequence[_SRT
             raise ValueError("fan_out_fec: a RED record of %r" % (x,))
     return _fan_out(pkts, transformers, rewriters, exclusion, stampers, payload=True, payers=payers, reds=reds,
                     fecs=fecs)
+
+
+def _seq_cmp(a: int, b: int) -> int:
+    """FECReceiver.seqNumComparator (transform/fec/FECReceiver.java:49-74)."""
+    if a == b:
+        return 0
+    if a > b:
+        return 1 if a - b < 32768 else -1
+    return -1 if b - a < 32768 else 1
+
+
+class FecReceiver:
+    """FECReceiver's state for one SSRC (transform/fec/FECReceiver.java): the
+    media packets (at most 64) and ulpfec packets (at most 32) kept across
+    :meth:`reverse_transform` calls as host bytes by sequence number, ``nb_fec``
+    ulpfec packets received and ``nb_recovered`` media packets recovered.
+    ``ulpfec_pt`` is the ulpfec payload type.  The maps are the reference's
+    TreeMaps under seqNumComparator (:49-74): the first key is the oldest of a
+    set that spans fewer than 2^15 sequence numbers, as the Java comment
+    demands of its input.  Every decision and every XOR is the GPU's
+    (:meth:`SRTPEngine.fec_recover_host`, Reconstructor.setFecPacket :472-520
+    and recover :527-596); ``engine`` defaults to :meth:`SRTPEngine.default`."""
+
+    MEDIA_BUF_SIZE, FEC_BUF_SIZE = 64, 32  # :114-127
+
+    def __init__(self, ssrc: int, ulpfec_pt: int, engine: Optional["SRTPEngine"] = None):
+        if not 0 <= int(ulpfec_pt) <= 127:
+            raise ValueError("FecReceiver: a payload type above 127")
+        self.ssrc, self.ulpfec_pt = int(ssrc) & 0xFFFFFFFF, int(ulpfec_pt)
+        self.engine = engine
+        self.nb_fec = 0
+        self.nb_recovered = 0
+        self.media = {}  # sequence number -> bytes
+        self.fec = {}
+
+    @staticmethod
+    def _first_key(d):
+        return sorted(d, key=functools.cmp_to_key(_seq_cmp))[0]
+
+    def _save_fec(self, data: bytes) -> None:
+        """saveFec (:350-356)"""
+        if len(self.fec) >= self.FEC_BUF_SIZE:
+            del self.fec[self._first_key(self.fec)]
+        self.fec[int.from_bytes(data[2:4], "big")] = data
+
+    def _save_media(self, data: bytes) -> None:
+        """saveMedia (:364-389)"""
+        if len(self.media) >= self.MEDIA_BUF_SIZE:
+            del self.media[self._first_key(self.media)]
+        self.media[int.from_bytes(data[2:4], "big")] = data
+
+    def _recover(self, keys):
+        """One srtp_fec_recover_host call: a record per FEC packet of ``keys``, every kept media packet a
+        candidate of each.  Returns (codes, packets)."""
+        eng = self.engine if self.engine is not None else SRTPEngine.default()
+        packets = list(self.media.values()) + [self.fec[k] for k in keys]
+        m = len(self.media)
+        up = lambda v: (v + 15) & ~15
+        off = np.zeros(len(packets), np.uint32)
+        off[1:] = np.cumsum([up(len(p)) for p in packets[:-1]])
+        seg = np.zeros(int(off[-1]) + up(len(packets[-1])), np.uint8)
+        for o, p in zip(off, packets):
+            seg[int(o):int(o) + len(p)] = np.frombuffer(p, np.uint8)
+        length = np.array([len(p) for p in packets], np.uint32)
+        rec = np.zeros(len(keys), N.FEC_RECOVER_DTYPE)
+        for r in range(len(keys)):
+            rec[r] = (m + r, 0, self.ssrc, m, 1, 0)
+        # a recovered packet is shorter than its FEC packet: the payload lies inside it
+        out_cap = np.array([len(self.fec[k]) for k in keys], np.uint32)
+        out_off = np.zeros(len(keys), np.uint32)
+        out_off[1:] = np.cumsum([up(int(c)) for c in out_cap[:-1]])
+        out_seg = np.zeros(int(out_off[-1]) + up(int(out_cap[-1])), np.uint8)
+        out_len, out_status, code = eng.fec_recover_host(seg, off, length, length, rec, np.arange(m, dtype=np.int32),
+                                                         out_seg, out_off, out_cap)
+        got = [bytes(out_seg[int(o):int(o) + int(n)]) if c == N.FECRX_RECOVERED and s == N.STATUS_OK else None
+               for o, n, s, c in zip(out_off, out_len, out_status, code)]
+        return [int(c) for c in code], got
+
+    def reverse_transform(self, pkts: Sequence[Optional[RawPacket]]):
+        """FECReceiver.reverseTransform (:233-319) over packets that have been
+        unprotected: ulpfec packets are counted, kept and taken out of the
+        list, media packets are kept, and every kept ulpfec packet is asked, in
+        sequence order, whether its group is complete (it is dropped), lacks
+        exactly one packet (the packet is recovered, kept at once and put into
+        the list's first empty slot, or appended) or more (it waits).  The
+        reference's order -- a recovered packet is a media packet for the FEC
+        packets behind it -- is kept by repeating the call: all pending records
+        run at once, the results up to and including the first that recovered
+        stand, and the records behind it run again."""
+        out = list(pkts)
+        for i, pkt in enumerate(out):
+            if pkt is None:
+                continue
+            data = pkt.data()
+            if (data[1] & 0x7F) == self.ulpfec_pt:
+                self.nb_fec += 1
+                out[i] = None
+                self._save_fec(data)
+            else:
+                self._save_media(data)
+        pending = sorted(self.fec, key=functools.cmp_to_key(_seq_cmp))
+        remove = []
+        while pending:
+            codes, got = self._recover(pending)
+            again = []
+            for r, key in enumerate(pending):
+                if codes[r] in (N.FECRX_COMPLETE, N.FECRX_PARTIAL, N.FECRX_RECOVERED):
+                    remove.append(key)  # packetsToRemove (:274, :280)
+                if codes[r] == N.FECRX_RECOVERED and got[r] is not None:
+                    self.nb_recovered += 1
+                    self._save_media(got[r])
+                    rp = RawPacket(got[r], 0, len(got[r]))
+                    if None in out:
+                        out[out.index(None)] = rp
+                    else:
+                        out.append(rp)
+                    again = pending[r + 1:]
+                    break
+            pending = again
+        for key in remove:
+            self.fec.pop(key, None)
+        return out
 
 
 def _fec_entries(pkts, T, flags, rewrite, fecs):
